@@ -50,6 +50,9 @@ FLOP_KEY = 40  # FP32 FLOP per nearest-node (Dubins) key
 FLOP_TILE_BOUND, FLOP_PREFILTER = 40, 12
 # BATCH option defer_steps of the headline run (a config may set its own)
 DEFER_STEPS = 128
+# --dump-outputs: nodes of the last timed query's tree written out (160 B per node, 21 MB); cfg3 appends this many
+# in the first ~0.1 s of its 2 s query
+DUMP_NODES = 1 << 17
 
 
 def parse():
@@ -63,15 +66,21 @@ def parse():
     ap.add_argument("--max-nodes", type=int, default=0,
                     help="tree capacity per rank (0: max(6 Mi, 2 Mi x N) -- the replicated tree grows N x faster)")
     ap.add_argument("--rows-per-node", type=int, default=64)
-    ap.add_argument("--cpu-queries", type=int, default=5, help="oracle queries timed for cpu_baseline")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-exact", action="store_true", help="skip the secondary EXACT-mode figure")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the secondary figures (1 GPU): cpu_baseline, exact_mode (with its replicas) and "
+                         "batch_sync; --no-cpu / --no-exact / --no-sync drop single ones.  Off: only the headline run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the tree the last timed query built (its first "
+                         f"{DUMP_NODES} nodes, in append order) as DIR/<field>.npy")
+    ap.add_argument("--cpu-queries", type=int, default=5, help="oracle queries timed for cpu_baseline (--full)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the cpu_baseline figure")
+    ap.add_argument("--no-exact", action="store_true", help="--full without the secondary EXACT-mode figure")
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--defer-steps", type=int, default=-1,
                     help="BATCH deferred samples: rollout chains run at most this many steps per round's launch, "
                          "longer ones resume in the next and their sample commits in a later round (0: off; "
                          "default: the config's, else DEFER_STEPS)")
-    ap.add_argument("--no-sync", action="store_true", help="skip the secondary figure without deferred samples")
+    ap.add_argument("--no-sync", action="store_true", help="--full without the secondary figure without deferred samples")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="N > 1: weak = batch samples per GPU per round (N x batch per round), strong = batch "
                          "samples per round split over the GPUs")
@@ -79,7 +88,30 @@ def parse():
                     help="gloo: rehearse the multi-rank path (e.g. several ranks sharing one GPU)")
     ap.add_argument("--opt", action="append", default=[], metavar="KEY=VALUE",
                     help="clrrt_set_option before the run (A/B of scheduling options; results do not change)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+def dump_outputs(pl, out_dir):
+    """--dump-outputs: the tree of the last timed query as a caller downloads it (clrrt_tree_download), one .npy per
+    node field, float64 (the int32 fields exactly) and float32 for the two float costs.  Only the first DUMP_NODES
+    nodes in append order: a query ends on its wall-clock horizon, so the tree's length differs from run to run,
+    but BATCH rounds are deterministic and what they append is the same for the same seed, so this prefix
+    (reached a fraction of the way into a query) compares equal between two runs or two builds.  The owner and
+    row-offset fields say where a node's rows are stored, not what was computed, and are left out.  With
+    replanning (cfg5) a query starts from the path the previous query found within its horizon, so there the
+    dump is a record of the run, not reproducible."""
+    import numpy as np
+    import clrrt
+    n = min(pl.size()[0], DUMP_NODES)
+    t = clrrt.nodes_to_numpy(pl.nodes_raw(0, n))
+    os.makedirs(out_dir, exist_ok=True)
+    for name in ("state", "ref_front", "ref_back", "ref_vback", "ang_par", "parent", "goal", "nrows"):
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(t[name], dtype=np.float64))
+    for name in ("costE", "costS"):
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(t[name], dtype=np.float32))
 
 
 def source_fingerprint():
@@ -361,15 +393,17 @@ def main():
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
 
+    # --full: the secondary figures beside the headline run (1 GPU only)
+    full = args.full and world == 1
     # the CPU baseline runs first, before this process touches the GPU (its replicas are separate
     # processes; nothing else competes for the host cores while it runs)
     cpu_line = None
-    if world == 1 and not args.no_cpu:
+    if full and not args.no_cpu:
         cpu_line = cpu_baseline(args.config, horizon, args.cpu_queries, args.seed)
     # EXACT mode the way the CPU baseline's replicas run the reference: as many independent planner processes as
     # the CPU replicas (at most 16 share the GPU), also before this process touches the GPU
     exact_rep = None
-    if world == 1 and not args.no_exact and not cfg.get("replan"):
+    if full and not args.no_exact and not cfg.get("replan"):
         exact_rep = gpu_exact_replicas(args.config, horizon, min(16, cpu_share()), args.seed)
 
     import torch
@@ -484,6 +518,9 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(pl, args.dump_outputs)
+
     trees_identical = None
     if world > 1:
         # every rank appended the same records in the same order: compare the trees of the last query
@@ -521,7 +558,7 @@ def main():
     sw = pl.search_work_ex()
 
     sync_line = None
-    if world == 1 and not replanning and not args.no_sync and defer > 0:
+    if full and not replanning and not args.no_sync and defer > 0:
         # secondary figure: plain BATCH rounds (every sample commits in its own round), one query from a
         # fresh tree, same scene, horizon and seed
         pl.set_option("defer_steps", 0)
@@ -534,7 +571,7 @@ def main():
         pl.set_option("defer_steps", defer)
 
     exact_line = None
-    if world == 1 and not replanning and not args.no_exact:
+    if full and not replanning and not args.no_exact:
         # secondary figure: EXACT mode (the reference's sequential expandTree tree, bit for bit) on the
         # same scene and horizon, one query from a fresh tree
         pl.tree_init()

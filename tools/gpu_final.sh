@@ -25,8 +25,8 @@ timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $out/t
   --warmup 1 --no-cpu --no-exact --no-sync > $out/trace_bench.json 2> $out/trace_bench.err
 rm -f $out/trace/p_kernel_trace.csv
 echo trace done
-timeout -k 10 400 python3 -u bench.py > $out/cfg3_bench.json 2> $out/cfg3_bench.err
+timeout -k 10 400 python3 -u bench.py --full > $out/cfg3_bench.json 2> $out/cfg3_bench.err
 cut -c1-200 $out/cfg3_bench.json
-timeout -k 10 200 python3 -u bench.py --config cfg2 --steps 10 --warmup 2 --no-cpu > $out/cfg2_bench.json 2> $out/cfg2_bench.err
-timeout -k 10 200 python3 -u bench.py --config cfg5 --steps 5 --warmup 1 --no-cpu > $out/cfg5_bench.json 2> $out/cfg5_bench.err
+timeout -k 10 200 python3 -u bench.py --full --config cfg2 --steps 10 --warmup 2 --no-cpu > $out/cfg2_bench.json 2> $out/cfg2_bench.err
+timeout -k 10 200 python3 -u bench.py --full --config cfg5 --steps 5 --warmup 1 --no-cpu > $out/cfg5_bench.json 2> $out/cfg5_bench.err
 echo all done

@@ -9,10 +9,10 @@ tag=${1:-r06zz}
 out=gpurun_out/$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-timeout -k 10 500 python3 -u bench.py > $out/cfg3_bench.json 2> $out/cfg3_bench.err
+timeout -k 10 500 python3 -u bench.py --full > $out/cfg3_bench.json 2> $out/cfg3_bench.err
 cut -c1-200 $out/cfg3_bench.json
-timeout -k 10 200 python3 -u bench.py --config cfg2 --steps 10 --warmup 2 --no-cpu > $out/cfg2_bench.json 2> $out/cfg2_bench.err
-timeout -k 10 200 python3 -u bench.py --config cfg5 --steps 5 --warmup 1 --no-cpu > $out/cfg5_bench.json 2> $out/cfg5_bench.err
+timeout -k 10 200 python3 -u bench.py --full --config cfg2 --steps 10 --warmup 2 --no-cpu > $out/cfg2_bench.json 2> $out/cfg2_bench.err
+timeout -k 10 200 python3 -u bench.py --full --config cfg5 --steps 5 --warmup 1 --no-cpu > $out/cfg5_bench.json 2> $out/cfg5_bench.err
 timeout -k 10 300 python3 -u -c "import __graft_entry__ as g; g.smoke()" > $out/smoke.log 2>&1
 tail -n 2 $out/smoke.log
 echo all done

@@ -10,4 +10,4 @@ timeout -k 10 900 python -u -m pytest tests/test_gpu_parity.py tests/test_ref_tr
   tests/test_native_capi.py tests/test_native_plan_motion.py -m gpu -v -s --timeout 600 --timeout-method thread \
   --maxfail=4 > $out/gpu_tests.log 2>&1 || rc=$?
 if [ "${rc:-0}" -gt 1 ]; then echo "pytest rc=$rc"; exit $rc; fi
-timeout -k 10 400 python3 -u bench.py --steps 3 --warmup 1 --no-cpu > $out/cfg3_bench.json 2> $out/cfg3_bench.err
+timeout -k 10 400 python3 -u bench.py --full --steps 3 --warmup 1 --no-cpu > $out/cfg3_bench.json 2> $out/cfg3_bench.err

@@ -10,4 +10,4 @@ timeout -k 10 900 python -u -m pytest tests/test_gpu_parity.py tests/test_full_s
   -k "walk or cfg3 or bench_settings" -v -s --timeout 900 --timeout-method thread -x > $out/gpu_tests.log 2>&1
 timeout -k 10 300 python3 -u tools/nn_large.py 4.7 16 > $out/nn_large_share.txt 2>&1
 CLRRT_LIB=cl-rrt_amd/prof_ab/libclrrt.so timeout -k 10 300 python3 -u tools/nn_large.py 4.7 16 > $out/nn_large_noshare.txt 2>&1
-timeout -k 10 300 python3 -u bench.py > $out/bench.json 2> $out/bench.err
+timeout -k 10 300 python3 -u bench.py --full > $out/bench.json 2> $out/bench.err

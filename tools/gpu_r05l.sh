@@ -11,6 +11,6 @@ timeout -k 10 200 python3 -u tools/step_latency.py > $out/step_latency_sparse.tx
 CLRRT_LIB=cl-rrt_amd/prof_ab/libclrrt.so timeout -k 10 200 python3 -u tools/step_latency.py > $out/step_latency_base.txt 2>&1
 timeout -k 10 200 python3 -u tools/exact_fixup_stats.py 2000 default > $out/exact_sparse.txt 2>&1
 CLRRT_LIB=cl-rrt_amd/prof_ab/libclrrt.so timeout -k 10 200 python3 -u tools/exact_fixup_stats.py 2000 default > $out/exact_base.txt 2>&1
-timeout -k 10 300 python3 -u bench.py --no-cpu > $out/bench_sparse.json 2> $out/bench_sparse.err
-CLRRT_LIB=cl-rrt_amd/prof_ab/libclrrt.so timeout -k 10 300 python3 -u bench.py --no-cpu > $out/bench_base.json 2> $out/bench_base.err
+timeout -k 10 300 python3 -u bench.py --full --no-cpu > $out/bench_sparse.json 2> $out/bench_sparse.err
+CLRRT_LIB=cl-rrt_amd/prof_ab/libclrrt.so timeout -k 10 300 python3 -u bench.py --full --no-cpu > $out/bench_base.json 2> $out/bench_base.err
 echo done

@@ -10,7 +10,7 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 for v in base rollnolicm; do
   lib=cl-rrt_amd/libclrrt.so
   [ $v = rollnolicm ] && lib=cl-rrt_amd/var_rollnolicm/libclrrt.so
-  CLRRT_LIB=$lib timeout -k 10 400 python3 -u bench.py --steps 5 --warmup 1 --no-cpu > $out/cfg3_bench_$v.json \
+  CLRRT_LIB=$lib timeout -k 10 400 python3 -u bench.py --full --steps 5 --warmup 1 --no-cpu > $out/cfg3_bench_$v.json \
     2> $out/cfg3_bench_$v.err
   cut -c1-120 $out/cfg3_bench_$v.json
   CLRRT_LIB=$lib timeout -k 10 200 python3 -u tools/step_latency.py > $out/step_latency_$v.txt 2>&1

@@ -26,7 +26,7 @@ for v in base rollnolicm; do
   lib=cl-rrt_amd/libclrrt.so
   [ $v = rollnolicm ] && lib=cl-rrt_amd/var_rollnolicm/libclrrt.so
   CLRRT_LIB=$lib timeout -k 10 200 python3 -u tools/step_latency.py > $out/step_latency_$v.txt 2>&1
-  CLRRT_LIB=$lib timeout -k 10 300 python3 -u bench.py --steps 1 --warmup 1 --no-cpu --no-sync \
+  CLRRT_LIB=$lib timeout -k 10 300 python3 -u bench.py --full --steps 1 --warmup 1 --no-cpu --no-sync \
     > $out/cfg3_exact_$v.json 2> $out/cfg3_exact_$v.err
 done
 echo done

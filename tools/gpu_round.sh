@@ -9,7 +9,7 @@ mkdir -p $out
 if [ "${2:-}" != "skip_tests" ]; then
   timeout -k 10 800 python -u -m pytest tests -m gpu -v -s --timeout 300 --timeout-method thread > $out/gpu_tests.log 2>&1
 fi
-timeout -k 10 400 python3 -u bench.py > $out/cfg3_bench.json 2> $out/cfg3_bench.err
+timeout -k 10 400 python3 -u bench.py --full > $out/cfg3_bench.json 2> $out/cfg3_bench.err
 timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof -o p \
   -- python3 -u bench.py --steps 2 --warmup 1 --no-cpu --no-exact > $out/cfg3_rocprof_bench.json 2> $out/rocprof.err
 for cfgname in cfg3 cfg2; do
@@ -29,6 +29,6 @@ for g in "$g_waits" "$g_mix"; do
     -d $out/pmc_sq/g$i -o p \
     -- python3 -u bench.py --steps 1 --warmup 0 --no-cpu --no-exact --horizon-ms 500 > $out/pmc_sq_g$i.log 2>&1
 done
-timeout -k 10 300 python3 -u bench.py --config cfg5 > $out/cfg5_bench.json 2> $out/cfg5_bench.err
-timeout -k 10 240 python3 -u bench.py --config cfg2 > $out/cfg2_bench.json 2> $out/cfg2_bench.err
+timeout -k 10 300 python3 -u bench.py --full --config cfg5 > $out/cfg5_bench.json 2> $out/cfg5_bench.err
+timeout -k 10 240 python3 -u bench.py --full --config cfg2 > $out/cfg2_bench.json 2> $out/cfg2_bench.err
 echo done

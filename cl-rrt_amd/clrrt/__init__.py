@@ -487,7 +487,7 @@ class Planner:
         return out[:n.value]
 
     def walk_audit(self, samples):
-        """clrrt_walk_audit (diagnostics): per sample (n, 12) int32 -- tiles with bound <= the true 11th key kth,
+        """clrrt_walk_audit (diagnostics): per sample (n, 20) int32 (columns 18, 19 unused) -- tiles with bound <= the true 11th key kth,
         those holding a list member, feasible records with key <= kth, records past the stage-1 bound at kth,
         super-tiles with bound <= kth, explore flag, kth bits, records of the admissible tiles, of which
         infeasible / farther than kth / within kth but key > kth, admissible tiles holding a record with key <= kth,

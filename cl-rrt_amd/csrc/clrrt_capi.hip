@@ -238,17 +238,20 @@ struct clrrt_ctx {
   // highest priority and the walk streams (side, side2) its lowest, so the commit and merge kernels are
   // not queued behind thousands of walk waves (kernel trace: k_select 16 us -> 1.9 ms late in a query)
   hipStream_t mst = nullptr;
-  // option "nn_split_delta" (default 0, round 6): the appended-node search of a slot is split by commit.  The
-  // nodes a commit appends are searched for the round-after-next's samples (slot B) on mst as soon as that slot's
-  // walk is done (its list seeds the chunk caps: unseeded, the search costs ~4x, profiles/r06l_*), beside the next
-  // round's rollouts; after the next commit only that commit's nodes remain, and the walk list, the first partial
-  // lists and the second are merged.  Round 5's single search of both commits' nodes started after the walk and
-  // was ~1.2 ms of the round's critical path (profiles/r06j_*).  (A fifth stream of its own for the first searches
-  // made every rollout kernel ~60% slower, split or not -- 4.1 vs 2.6 ms per round, profiles/r06n_*; not the
-  // hardware queue count: GPU_MAX_HW_QUEUES 2 / 4 / 8 / 16 leave the default build unchanged, r06p_*.)  On mst the lists are
-  // the same and the round is not faster (cfg3 1.281 / 1.275 vs 1.292 M nodes/s, list wait 1.06 / 0.95 vs 1.08 ms,
-  // profiles/r06o_*): the lists wait for the walk, not for this search.
-  int nn_split_delta = 0;
+  // (Round 6 also split the appended-node search by commit, option "nn_split_delta": the lists were the same and the
+  // round no faster -- the GPU is work-bound there, profiles/r06o_* -- so the path is gone.)
+  // option "nn_delta_walk" (default 1): the lag-2 appended-node search walks a place-ordered index of the appended
+  // range (launch_nn_delta_walk, buffer set nnw_d) instead of brute-forcing every (sample, appended node) pair
+  // (k_nn_partial: 0, and the fallback where the walk's preconditions fail).  Same lists either way.
+  int nn_delta_walk = 1;
+  // option "nn_delta_verify" (diagnostics, default 0): every appended-node walk is followed by the brute force over
+  // the same range and caps, and k_nn_delta_compare counts the samples compared / differing in work counters 38 / 39
+  // (the walk's own statistics go to counters 40..52, the brute force's queued pairs and exact keys to 54 / 55).
+  int nn_delta_verify = 0;
+  WalkBufs nnw_d{};
+  float* vpk = nullptr;    // nn_delta_verify: the brute force's chunk lists (partial_cap entries) ...
+  int* vpi = nullptr;
+  float* vseed = nullptr;  // ... and its copy of the caps (k_nn_partial lowers them)
   // option "nn_delta_early" (default 1, round 6): the appended-node search of a slot starts after its walk's main grid
   // (key caps from k_walk_seed, per slot in wseed) instead of after the overflow split and its merge, so it runs beside
   // the split (a cfg3 trace: main grid done 1.7 ms before the rollout kernel, split until 0.6 ms after it, the search
@@ -260,11 +263,6 @@ struct clrrt_ctx {
   int* nn_order = nullptr;  // [max_batch]
   float* wseed[3] = {nullptr, nullptr, nullptr};      // per slot: [max_batch] caps taken after the main walk grid
   hipEvent_t ev_wm[3] = {nullptr, nullptr, nullptr};  // per slot: recorded after the main walk grid (and wseed)
-  float* nn_seed2 = nullptr;                   // [max_batch] the first searches' chunk caps
-  float* d1pk[3] = {nullptr, nullptr, nullptr};  // per slot: the first partial lists (partial_cap entries)
-  int* d1pi[3] = {nullptr, nullptr, nullptr};
-  hipEvent_t ev_d1[3] = {nullptr, nullptr, nullptr};  // recorded after a slot's first partial search
-  hipEvent_t ev_s[3] = {nullptr, nullptr, nullptr};   // recorded after a slot's samples reached the device
   hipEvent_t ev_lagw[3] = {nullptr, nullptr, nullptr};
   int stream_prio = 1;
   int walk_cu_reserve = 0;  // option "walk_cu_reserve" k = 1..7: lag-2 walk streams kept off k/8 of the CUs
@@ -636,15 +634,17 @@ static void free_all(clrrt_ctx* c) {
   if (c->mst) hipStreamSynchronize(c->mst);
   if (c->mst) hipStreamDestroy(c->mst);
   for (int q = 0; q < 3; q++) {
-    if (c->ev_d1[q]) hipEventDestroy(c->ev_d1[q]);
-    if (c->ev_s[q]) hipEventDestroy(c->ev_s[q]);
-    if (c->d1pk[q]) hipFree(c->d1pk[q]);
     if (c->wseed[q]) hipFree(c->wseed[q]);
     if (q == 0 && c->nn_order) hipFree(c->nn_order);
     if (c->ev_wm[q]) hipEventDestroy(c->ev_wm[q]);
-    if (c->d1pi[q]) hipFree(c->d1pi[q]);
   }
-  if (c->nn_seed2) hipFree(c->nn_seed2);
+  {
+    WalkBufs& d = c->nnw_d;
+    void* wd[] = {d.keys, d.vals, d.tmp, d.P, d.Q, d.CE, d.ID, d.HEAD, d.trun, d.tiles, d.supers, d.skeys, d.sids,
+                  c->vpk, c->vpi, c->vseed};
+    for (void* p : wd)
+      if (p) hipFree(p);
+  }
   if (c->side) hipStreamSynchronize(c->side);
   if (c->ev_tree) hipEventDestroy(c->ev_tree);
   if (c->ev_walk) hipEventDestroy(c->ev_walk);
@@ -1433,7 +1433,8 @@ int clrrt_set_option(clrrt_ctx* c, const char* key, int64_t value) {
   }
   else if (k == "nn_walk_double") c->nnw_double = value != 0;
   else if (k == "nn_lag" && (value == 0 || value == 1 || value == 2)) c->nn_lag = (int)value;
-  else if (k == "nn_split_delta") c->nn_split_delta = value != 0 ? 1 : 0;  // scheduling only: same lists
+  else if (k == "nn_delta_walk") c->nn_delta_walk = value != 0 ? 1 : 0;  // same lists either way
+  else if (k == "nn_delta_verify") c->nn_delta_verify = value != 0 ? 1 : 0;  // diagnostics: counters 38 / 39
   else if (k == "nn_delta_early") c->nn_delta_early = value != 0 ? 1 : 0;  // scheduling only: same lists
   else if (k == "nn_lane_order") c->nn_lane_order = value != 0 ? 1 : 0;  // scheduling only: same lists
   else if (k == "nn_debug" && value >= 0) c->nn_debug = (int)value;  // diagnostics: changes results
@@ -2714,13 +2715,6 @@ struct LagSlot {
   int64_t g = 0;            // samples of the round (all ranks)
   int64_t tree_n = 0;       // size of the tree its walk searched
   int stream = 0;           // side stream index
-  // nn_split_delta: the first partial search (the nodes of the commit after its walk's tree), its lists and events
-  float* d1pk = nullptr;
-  int* d1pi = nullptr;
-  int d1_chunks = 0;
-  int64_t d1_count = 0;     // nodes it covered ([tree_n, tree_n + d1_count)); 0: none
-  hipEvent_t evd1 = nullptr;
-  hipEvent_t evs = nullptr; // the samples are on the device
   // nn_delta_early: the appended-node search's caps taken after the walk's main grid, and the event recorded there
   float* wseed = nullptr;
   hipEvent_t evm = nullptr;
@@ -2747,15 +2741,45 @@ static int lag_alloc(clrrt_ctx* c) {
     HIPC(c, hipStreamCreateWithFlags(&c->side2, hipStreamNonBlocking));
   }
   HIPC(c, hipStreamCreateWithFlags(&c->mst, hipStreamNonBlocking));
-  HIPC(c, dalloc(&c->nn_seed2, B));
   for (int q = 0; q < 3; q++) {
-    HIPC(c, dalloc(&c->d1pk[q], c->partial_cap));
     HIPC(c, dalloc(&c->wseed[q], B));
     if (q == 0) HIPC(c, dalloc(&c->nn_order, B));
     HIPC(c, hipEventCreateWithFlags(&c->ev_wm[q], hipEventDisableTiming));
-    HIPC(c, dalloc(&c->d1pi[q], c->partial_cap));
-    HIPC(c, hipEventCreateWithFlags(&c->ev_d1[q], hipEventDisableTiming));
-    HIPC(c, hipEventCreateWithFlags(&c->ev_s[q], hipEventDisableTiming));
+  }
+  return CLRRT_OK;
+}
+
+// The appended-node walk's index set (nnw_d: the buffers launch_nn_delta_walk uses, for walk_delta_cap nodes) and,
+// with nn_delta_verify, the brute force's buffers beside it.
+static int alloc_walk_delta(clrrt_ctx* c) {
+  WalkBufs& w = c->nnw_d;
+  if (!w.P) {
+    const int64_t cap = walk_delta_cap(c->cap.max_nodes, c->cap.max_batch);
+    const int64_t Mp = walk_tile_count(cap) * 32;  // the padded records
+    HIPC(c, dalloc(&w.keys, 2 * cap));
+    HIPC(c, dalloc(&w.vals, cap));
+    w.tmp_bytes = walk_sort_bytes((int)cap);
+    HIPC(c, hipMalloc(&w.tmp, std::max<size_t>(w.tmp_bytes, 256)));
+    HIPC(c, dalloc(&w.skeys, cap));
+    HIPC(c, dalloc(&w.sids, cap));
+    HIPC(c, dalloc(&w.Q, Mp));
+    HIPC(c, dalloc(&w.CE, Mp));
+    HIPC(c, dalloc(&w.ID, Mp));
+    HIPC(c, dalloc(&w.HEAD, Mp));
+    HIPC(c, dalloc(&w.trun, walk_tile_count(cap)));
+    HIPC(c, dalloc(&w.tiles, walk_tile_count(cap)));
+    HIPC(c, dalloc(&w.supers, walk_super_count(cap)));
+    w.sorted_n = -1;
+    w.cap_nodes = cap;
+    w.cap_batch = (int)c->cap.max_batch;
+    HIPC(c, dalloc(&w.P, Mp));  // last: marks the set complete
+  }
+  w.index_kind = c->nnw_index;
+  w.hscale_pct = c->nnw_hscale;
+  if (c->nn_delta_verify && !c->vseed) {
+    HIPC(c, dalloc(&c->vpk, c->partial_cap));
+    HIPC(c, dalloc(&c->vpi, c->partial_cap));
+    HIPC(c, dalloc(&c->vseed, c->cap.max_batch));
   }
   return CLRRT_OK;
 }
@@ -2798,6 +2822,7 @@ static int apply_stream_prio(clrrt_ctx* c) {
 static int expand_lag2(clrrt_ctx* c, clrrt_rng* rng, int64_t n_iters, double budget_ms, int32_t batch,
                        clrrt_stats* out) {
   int rc = lag_alloc(c);
+  if (rc == CLRRT_OK && c->nn_delta_walk) rc = alloc_walk_delta(c);
   if (rc == CLRRT_OK) rc = apply_stream_prio(c);
   if (rc == CLRRT_OK) rc = defer_begin(c, true);
   if (rc != CLRRT_OK) return rc;
@@ -2823,8 +2848,6 @@ static int expand_lag2(clrrt_ctx* c, clrrt_rng* rng, int64_t n_iters, double bud
   A.ctie = c->ctie2; A.ev = c->ev_lag[0]; A.evw = c->ev_lagw[0];
   B.d = c->d_samples3; B.h = c->h_samples3; B.cand = c->cand3; B.ckey = c->ckey3; B.ncand = c->ncand3;
   B.ctie = c->ctie3; B.ev = c->ev_lag[1]; B.evw = c->ev_lagw[1];
-  A.d1pk = c->d1pk[0]; A.d1pi = c->d1pi[0]; A.evd1 = c->ev_d1[0]; A.evs = c->ev_s[0];
-  B.d1pk = c->d1pk[1]; B.d1pi = c->d1pi[1]; B.evd1 = c->ev_d1[1]; B.evs = c->ev_s[1];
   A.wseed = c->wseed[0]; A.evm = c->ev_wm[0];
   B.wseed = c->wseed[1]; B.evm = c->ev_wm[1];
   float* cur_wseed = c->wseed[2];
@@ -2832,10 +2855,11 @@ static int expand_lag2(clrrt_ctx* c, clrrt_rng* rng, int64_t n_iters, double bud
   const bool early = c->nn_delta_early != 0;
   hipEvent_t cur_ev = c->ev_lag[2];  // the event of the set this round's lists are in
   hipEvent_t cur_evw = c->ev_lagw[2];
-  float* cur_d1pk = c->d1pk[2];       // ... and that set's split-delta buffers and events
-  int* cur_d1pi = c->d1pi[2];
-  hipEvent_t cur_evd1 = c->ev_d1[2], cur_evs = c->ev_s[2];
-  const bool split_delta = c->nn_split_delta != 0;
+  // The appended-node search walks its range's own index (nn_delta_walk) from one tile of appended nodes on: a range
+  // inside one tile has a single bound, so the walk would prefilter every record as k_nn_partial does, behind three
+  // more launches (a range above the set's capacity takes the brute force too).
+  const int64_t delta_walk_min = 32;
+  const bool delta_walk = c->nn_delta_walk != 0;
   // The three list sets rotate every round; whichever way the function is left (an error return of HIPC
   // included), the buffers the context's other paths use get their roles back: (d_samples, cand, ...) and
   // the *2 set are whichever two of the three sets, *3 the third, each freed once by free_all.
@@ -2885,9 +2909,6 @@ static int expand_lag2(clrrt_ctx* c, clrrt_rng* rng, int64_t n_iters, double bud
     c->nn_samples += n;
     HIPC(c, hipStreamWaitEvent(s, c->ev_tree, 0));
     HIPC(c, hipMemcpyAsync(sl.d, sl.h, sizeof(clrrt_sample) * n, hipMemcpyHostToDevice, s));
-    HIPC(c, hipEventRecord(sl.evs, s));  // (the split delta's first search reads them on mst)
-    sl.d1_count = 0;
-    sl.d1_chunks = 0;
     c->nn_super_bounds += (int64_t)n * walk_super_count(c->n_nodes);
     {
       KTimer kt(c, 0, s), kt3(c, 3, s);
@@ -3006,94 +3027,54 @@ static int expand_lag2(clrrt_ctx* c, clrrt_rng* rng, int64_t n_iters, double bud
     if ((rc = compact_and_copy(c, L, &nn, true)) != CLRRT_OK) break;
     const double ms_commit = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     if ((rc = commit_round(c, nn, ms_commit, &n_app)) != CLRRT_OK) break;
-    // slot A: merge the nodes appended since its walk's tree
-    if ((A.n > 0 || (split_delta && B.n > 0)))
+    // slot A: merge the nodes appended since its walk's tree.  On the merge stream, behind the commit and -- early --
+    // slot A's main walk grid (caps from its k_walk_seed, beside the walk's overflow split) or the whole walk (caps from
+    // its list); the merge behind the whole walk.  The search walks the range's own index (launch_nn_delta_walk) where
+    // the walk is served (region, tree size) and the range is neither tiny nor beyond the set; else the brute force.
+    if (A.n > 0) {
       HIPC(c, hipEventRecord(c->ev_commit, c->stream));
-    if (A.n > 0 && split_delta) {
-      // the nodes its first partial search did not cover (this commit's), their key caps seeded from its walk list;
-      // then the walk list, the first partial lists and these are merged
       hipStream_t s = c->mst;
       HIPC(c, hipStreamWaitEvent(s, c->ev_commit, 0));
       HIPC(c, hipStreamWaitEvent(s, early ? A.evm : A.evw, 0));
-      const int64_t first2 = A.tree_n + A.d1_count, cnt2 = c->n_nodes - first2;
-      int nch2 = 0;
-      if (cnt2 > 0) {
-        KTimer kt(c, 0, s);
-        c->nn_bf_keys += (int64_t)A.n * cnt2;
-        const NnSetup su2 = nn_setup(c);
-        const int max_chunks = (int)std::max<int64_t>(1, c->partial_cap / ((int64_t)A.n * NN_K));
-        HIPC(c, launch_nn_delta_partial(s, A.d, A.n, c->nn, (int)first2, (int)cnt2, c->dp, su2.fr, c->pk, c->pi,
-                                        max_chunks, A.ckey, A.ncand, early ? A.wseed : c->nn_seed, early,
-                                        c->nn_lane_order ? c->nn_order : nullptr, &nch2));
-      }
-      if (early) HIPC(c, hipStreamWaitEvent(s, A.evw, 0));
-      if (A.d1_count > 0) HIPC(c, hipStreamWaitEvent(s, A.evd1, 0));
-      {
-        KTimer kt(c, 0, s);
-        if (A.d1_count > 0)
-          HIPC(c, launch_nn_delta_merge(s, A.n, A.d1_chunks, c->dp, A.d1pk, A.d1pi, (int)A.tree_n, A.cand, A.ckey,
-                                        A.ncand, A.ctie));
-        HIPC(c, launch_nn_delta_merge(s, A.n, nch2, c->dp, c->pk, c->pi, (int)first2, A.cand, A.ckey, A.ncand, A.ctie));
-      }
-      HIPC(c, hipEventRecord(A.ev, s));
-    } else if (A.n > 0 && early) {
-      // behind the commit and slot A's main walk grid (caps from its k_walk_seed), beside the walk's overflow split;
-      // the merge behind the whole walk
-      hipStream_t s = c->mst;
-      HIPC(c, hipStreamWaitEvent(s, c->ev_commit, 0));
-      HIPC(c, hipStreamWaitEvent(s, A.evm, 0));
       const int64_t first = A.tree_n, cnt = c->n_nodes - A.tree_n;
-      int nch = 0;
-      if (cnt > 0) {
+      const NnSetup su2 = nn_setup(c);
+      const bool dwalk = delta_walk && su2.region_ok && c->n_nodes >= c->nnw_min_nodes && cnt >= delta_walk_min &&
+                         cnt <= c->nnw_d.cap_nodes;
+      const int max_chunks = (int)std::max<int64_t>(1, c->partial_cap / ((int64_t)A.n * NN_K));
+      int nch = 0, id0 = (int)first;
+      if (cnt > 0) c->nn_bf_keys += (int64_t)A.n * cnt;
+      if (cnt > 0 && dwalk) {
         KTimer kt(c, 0, s);
-        c->nn_bf_keys += (int64_t)A.n * cnt;
-        const NnSetup su2 = nn_setup(c);
-        const int max_chunks = (int)std::max<int64_t>(1, c->partial_cap / ((int64_t)A.n * NN_K));
+        float* seed = early ? A.wseed : c->nn_seed;
+        const bool verify = c->nn_delta_verify && c->vseed;
+        HIPC(c, launch_nn_delta_walk(s, A.d, A.n, c->nn, (int)first, (int)cnt, c->dp, su2.fr, su2.x0, su2.y0, su2.x1,
+                                     su2.y1, c->nnw_d, c->pk, c->pi, A.ckey, A.ncand, seed, early,
+                                     verify ? c->work_ctr + 40 : nullptr));
+        nch = 1;
+        id0 = 0;
+        if (verify) {  // the brute force over the same range and caps, and the two list sets compared
+          int vch = 0;
+          HIPC(c, hipMemcpyAsync(c->vseed, seed, sizeof(float) * A.n, hipMemcpyDeviceToDevice, s));
+          HIPC(c, launch_nn_delta_partial(s, A.d, A.n, c->nn, (int)first, (int)cnt, c->dp, su2.fr, c->vpk, c->vpi,
+                                          max_chunks, nullptr, nullptr, c->vseed, true, nullptr, &vch, c->work_ctr + 52));
+          HIPC(c, launch_nn_delta_compare(s, A.n, vch, (int)first, c->vpk, c->vpi, c->pk, c->pi, c->work_ctr + 38));
+        }
+      } else if (cnt > 0 && early) {
+        KTimer kt(c, 0, s);
         HIPC(c, launch_nn_delta_partial(s, A.d, A.n, c->nn, (int)first, (int)cnt, c->dp, su2.fr, c->pk, c->pi,
                                         max_chunks, nullptr, nullptr, A.wseed, true,
                                         c->nn_lane_order ? c->nn_order : nullptr, &nch));
-      }
-      HIPC(c, hipStreamWaitEvent(s, A.evw, 0));
-      {
+      } else if (cnt > 0) {
         KTimer kt(c, 0, s);
-        HIPC(c, launch_nn_delta_merge(s, A.n, nch, c->dp, c->pk, c->pi, (int)first, A.cand, A.ckey, A.ncand, A.ctie));
-      }
-      HIPC(c, hipEventRecord(A.ev, s));
-    } else if (A.n > 0) {
-      hipStream_t s = c->mst;  // behind the commit and slot A's walk
-      HIPC(c, hipStreamWaitEvent(s, c->ev_commit, 0));
-      HIPC(c, hipStreamWaitEvent(s, A.evw, 0));
-      const int64_t first = A.tree_n, cnt = c->n_nodes - A.tree_n;
-      if (cnt > 0) {
-        KTimer kt(c, 0, s);
-        c->nn_bf_keys += (int64_t)A.n * cnt;
-        const NnSetup su2 = nn_setup(c);
-        const int max_chunks = (int)std::max<int64_t>(1, c->partial_cap / ((int64_t)A.n * NN_K));
         HIPC(c, launch_nn_delta(s, A.d, A.n, c->nn, (int)first, (int)cnt, c->dp, su2.fr, c->pk, c->pi, max_chunks,
                                 A.cand, A.ckey, A.ncand, A.ctie, c->nn_seed));
       }
-      HIPC(c, hipEventRecord(A.ev, s));
-    }
-    // slot B (split delta): this commit's nodes, searched for the round-after-next's samples beside the next
-    // round's rollouts (merged into B's list after the next commit, when B is slot A); behind slot A's merges
-    if (split_delta && B.n > 0) {
-      hipStream_t s2 = c->mst;
-      HIPC(c, hipStreamWaitEvent(s2, c->ev_commit, 0));
-      HIPC(c, hipStreamWaitEvent(s2, B.evs, 0));
-      HIPC(c, hipStreamWaitEvent(s2, early ? B.evm : B.evw, 0));  // (its walk list seeds the key caps)
-      const int64_t cnt1 = c->n_nodes - B.tree_n;
-      B.d1_count = cnt1;
-      B.d1_chunks = 0;
-      if (cnt1 > 0) {
-        KTimer kt(c, 0, s2);
-        c->nn_bf_keys += (int64_t)B.n * cnt1;
-        const NnSetup su1 = nn_setup(c);
-        const int max_chunks = (int)std::max<int64_t>(1, c->partial_cap / ((int64_t)B.n * NN_K));
-        HIPC(c, launch_nn_delta_partial(s2, B.d, B.n, c->nn, (int)B.tree_n, (int)cnt1, c->dp, su1.fr, B.d1pk, B.d1pi,
-                                        max_chunks, B.ckey, B.ncand, early ? B.wseed : c->nn_seed2, early,
-                                        c->nn_lane_order ? c->nn_order : nullptr, &B.d1_chunks));
+      if (early) HIPC(c, hipStreamWaitEvent(s, A.evw, 0));
+      if (nch > 0) {
+        KTimer kt(c, 0, s);
+        HIPC(c, launch_nn_delta_merge(s, A.n, nch, c->dp, c->pk, c->pi, id0, A.cand, A.ckey, A.ncand, A.ctie));
       }
-      HIPC(c, hipEventRecord(B.evd1, s2));
+      HIPC(c, hipEventRecord(A.ev, s));
     }
     // the next round's index (the walk of round r+3's samples searches it)
     {
@@ -3114,14 +3095,12 @@ static int expand_lag2(clrrt_ctx* c, clrrt_rng* rng, int64_t n_iters, double bud
       LagSlot old;
       old.d = c->d_samples; old.h = c->h_samples; old.cand = c->cand; old.ckey = c->ckey; old.ncand = c->ncand;
       old.ctie = c->ctie; old.ev = cur_ev; old.evw = cur_evw; old.stream = cur_stream;
-      old.d1pk = cur_d1pk; old.d1pi = cur_d1pi; old.evd1 = cur_evd1; old.evs = cur_evs;
       old.wseed = cur_wseed; old.evm = cur_evm;
       have_cur = A.n > 0;
       c->d_samples = A.d; c->h_samples = A.h; c->cand = A.cand; c->ckey = A.ckey; c->ncand = A.ncand; c->ctie = A.ctie;
       cur_ev = A.ev;
       cur_evw = A.evw;
       cur_stream = A.stream;
-      cur_d1pk = A.d1pk; cur_d1pi = A.d1pi; cur_evd1 = A.evd1; cur_evs = A.evs;
       cur_wseed = A.wseed; cur_evm = A.evm;
       A = B;
       B = old;

@@ -256,12 +256,26 @@ hipError_t launch_walk_audit(hipStream_t st, const clrrt_sample* S, int B, const
 hipError_t launch_nn_delta(hipStream_t st, const clrrt_sample* S, int B, const NnRec* nodes, int first, int count,
                            const DevParams& p, const NnFrame& fr, float* pk, int* pi, int max_chunks, int* cand,
                            float* ckey, int* ncand, int* ctie, float* seed);
+// The appended-node search as a walk (clrrt_nnwalk.hip): an index of nodes [first, first + count) alone in w (a set
+// of walk_delta_cap nodes; keys, sort, one fused index kernel) and one wave per sample walking it from the sample's
+// key cap in seed[B] (seeded: already there, k_walk_seed's; else taken from the older list ckey / ncand first).  The
+// lists go to pk / pi, NN_K entries per sample with the nodes' own ids: launch_nn_delta_merge with nchunks 1, id0 0.
+// (x0, y0, x1, y1): the Morton frame of nn_setup at this commit, fr its float frame.
+int64_t walk_delta_cap(int64_t max_nodes, int64_t max_batch);
+hipError_t launch_nn_delta_walk(hipStream_t st, const clrrt_sample* S, int B, const NnRec* nodes, int first, int count,
+                                const DevParams& p, const NnFrame& fr, double x0, double y0, double x1, double y1,
+                                WalkBufs& w, float* pk, int* pi, const float* ckey, const int* ncand, float* seed,
+                                bool seeded, unsigned long long* stats);
+// Option nn_delta_verify: the brute force's chunk lists (pk / pi, ids relative to id0) against the walk's lists (wk /
+// wi) of the same search; out[0] += samples compared, out[1] += samples whose NN_K (key bits, id) pairs differ.
+hipError_t launch_nn_delta_compare(hipStream_t st, int B, int nchunks, int id0, const float* pk, const int* pi,
+                                   const float* wk, const int* wi, unsigned long long* out);
 // launch_nn_delta split in two: the partial lists over the appended nodes (caps shared between chunks from +inf in
 // gcap[B], no older list needed; *nchunks_out lists per sample in pk / pi), and their merge into a list.
 hipError_t launch_nn_delta_partial(hipStream_t st, const clrrt_sample* S, int B, const NnRec* nodes, int first,
                                    int count, const DevParams& p, const NnFrame& fr, float* pk, int* pi, int max_chunks,
                                    const float* ckey, const int* ncand, float* gcap, bool seeded, int* order,
-                                   int* nchunks_out);
+                                   int* nchunks_out, unsigned long long* tstat = nullptr);
 hipError_t launch_nn_delta_merge(hipStream_t st, int B, int nchunks, const DevParams& p, const float* pk, const int* pi,
                                  int id0, int* cand, float* ckey, int* ncand, int* ctie);
 // Nearest-node search.  exact_scratch != nullptr (EXACT mode, B*N KeyId entries): samples whose

@@ -372,6 +372,35 @@ __global__ void k_nn_merge_delta(int B, int nchunks, int limit, const float* __r
   ctie[s] = tie;
 }
 
+// Option nn_delta_verify: the first NN_K pairs of a sample's brute-force chunk lists (ids relative to id0) against
+// the list the appended-node walk wrote for it (the nodes' own ids), key bit patterns and ids.
+__global__ void k_nn_delta_compare(int B, int nchunks, int id0, const float* __restrict__ pk,
+                                   const int* __restrict__ pi, const float* __restrict__ wk,
+                                   const int* __restrict__ wi, unsigned long long* __restrict__ out) {
+  const int s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= B) return;
+  float keys[NN_K];
+  int ids[NN_K];
+#pragma unroll
+  for (int j = 0; j < NN_K; j++) { keys[j] = __builtin_inff(); ids[j] = 0x7fffffff; }
+  for (int c = 0; c < nchunks; c++) {
+    const size_t base = ((size_t)s * nchunks + c) * NN_K;
+    for (int j = 0; j < NN_K; j++) {
+      const int id = pi[base + j];
+      if (id == 0x7fffffff) break;
+      const float k = pk[base + j];
+      if (lex_less(k, id + id0, keys[NN_K - 1], ids[NN_K - 1])) topk_insert(keys, ids, k, id + id0);
+      else break;  // chunk lists are sorted
+    }
+  }
+  bool bad = false;
+#pragma unroll
+  for (int j = 0; j < NN_K; j++)
+    bad |= __float_as_uint(keys[j]) != __float_as_uint(wk[(size_t)s * NN_K + j]) || ids[j] != wi[(size_t)s * NN_K + j];
+  atomicAdd(&out[0], 1ull);
+  if (bad) atomicAdd(&out[1], 1ull);
+}
+
 // EXACT mode, samples whose candidate selection involves equal keys: rebuild the full (id, key)
 // sequence in node order and replay libstdc++'s std::sort on it (one lane per sample), then walk it
 // exactly as sortNodesExplore/Optimize do (rrtplanner.cpp:237-243).
@@ -2883,15 +2912,15 @@ hipError_t launch_nn_delta(hipStream_t st, const clrrt_sample* S, int B, const N
   return hipSuccess;
 }
 
-// The appended-node search in two halves, for callers that split it (expand_lag2 with nn_split_delta): the partial
+// The brute-force appended-node search in two halves (expand_lag2 merges behind the whole walk): the partial
 // lists of samples S over nodes [first, first + count) -- the chunks' shared key caps in gcap seeded from the samples'
 // older list (ckey / ncand, the walk's: no node above its sort_limit-th key can enter; +inf without one, which costs
 // ~4x: k_nn_partial 4.9 vs 1.15 ms per cfg3 launch, profiles/r06l_*) -- and the merge of such partial lists (ids
-// relative to id0) into a list.  seeded: gcap already holds caps (no seed kernel).
+// relative to id0) into a list.  seeded: gcap already holds caps (no seed kernel).  tstat: k_nn_partial's counters.
 hipError_t launch_nn_delta_partial(hipStream_t st, const clrrt_sample* S, int B, const NnRec* nodes, int first,
                                    int count, const DevParams& p, const NnFrame& fr, float* pk, int* pi, int max_chunks,
                                    const float* ckey, const int* ncand, float* gcap, bool seeded, int* order,
-                                   int* nchunks_out) {
+                                   int* nchunks_out, unsigned long long* tstat) {
   *nchunks_out = 0;
   if (count <= 0 || B <= 0) return hipSuccess;
   const int* sord = nullptr;
@@ -2913,7 +2942,7 @@ hipError_t launch_nn_delta_partial(hipStream_t st, const clrrt_sample* S, int B,
     LAUNCH_CHECK();
   }
   hipLaunchKernelGGL(k_nn_partial, dim3(groups, nchunks), dim3(CLRRT_PATH_BLK), 0, st, S, B, nodes + first, count, chunk,
-                     nchunks, p, fr, pk, pi, gcap, nullptr, sord);
+                     nchunks, p, fr, pk, pi, gcap, tstat, sord);
   LAUNCH_CHECK();
   *nchunks_out = nchunks;
   return hipSuccess;
@@ -2923,6 +2952,14 @@ hipError_t launch_nn_delta_merge(hipStream_t st, int B, int nchunks, const DevPa
   if (nchunks <= 0 || B <= 0) return hipSuccess;
   hipLaunchKernelGGL(k_nn_merge_delta, dim3((B + 63) / 64), dim3(64), 0, st, B, nchunks, p.sort_limit, pk, pi, id0, cand,
                      ckey, ncand, ctie);
+  LAUNCH_CHECK();
+  return hipSuccess;
+}
+
+hipError_t launch_nn_delta_compare(hipStream_t st, int B, int nchunks, int id0, const float* pk, const int* pi,
+                                   const float* wk, const int* wi, unsigned long long* out) {
+  if (B <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_nn_delta_compare, dim3((B + 63) / 64), dim3(64), 0, st, B, nchunks, id0, pk, pi, wk, wi, out);
   LAUNCH_CHECK();
   return hipSuccess;
 }

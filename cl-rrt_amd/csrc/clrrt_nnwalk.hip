@@ -65,6 +65,9 @@ namespace clrrt {
 #ifndef WALK_SPLIT_SHARE
 #define WALK_SPLIT_SHARE 1  // the overflow split waves of one record share their bounds (round 5)
 #endif
+#ifndef CLRRT_DELTA_ONEPASS
+#define CLRRT_DELTA_ONEPASS 1  // the appended-node walk of a capped sample: one pass (cfg3 +1.0 % over growing passes)
+#endif
 #ifndef WALK_APBINS
 #define WALK_APBINS 8  // ang_par sectors (top key bits)
 #endif
@@ -292,16 +295,9 @@ __device__ __forceinline__ float wmin(float v) {
 
 // Bounds of `size` consecutive records per tile, one wave per tile.  `slack` inflates the discs by
 // the float frame's coordinate error so the bounds hold for the exact positions too.
-__global__ void __launch_bounds__(256) k_walk_tiles(const float4* __restrict__ P, const float4* __restrict__ Q,
-                                                    const float* __restrict__ CE, const int* __restrict__ ID,
-                                                    int ntiles, int size, float slack,
-                                                    const NnRec* __restrict__ nodes, double ox, double oy,
-                                                    WalkTile* __restrict__ out) {
-  // R = node 0's position in the frame (any fixed point gives a valid bound; the root gives a tight one)
-  const float Rx = (float)(nodes[0].x - ox), Ry = (float)(nodes[0].y - oy);
-  const int t = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);  // one wave per tile
-  const int lane = threadIdx.x & 63;
-  if (t >= ntiles) return;
+// (one wave: tile t of `size` records; R = (Rx, Ry), see k_walk_tiles)
+__device__ __forceinline__ void walk_tile_bounds(const float4* P, const float4* Q, const float* CE, const int* ID, int t,
+                                                 int size, float slack, float Rx, float Ry, int lane, WalkTile* out) {
   const int b = t * size;
   float spx = 0, spy = 0, srx = 0, sry = 0, sux = 0, suy = 0, sax = 0, say = 0, cnt = 0, bad = 0;
   for (int k = lane; k < size; k += 64) {
@@ -370,6 +366,79 @@ __global__ void __launch_bounds__(256) k_walk_tiles(const float4* __restrict__ P
   // R is a float frame point (exact as given); the node positions err by the frame's slack
   w.eroot = eroot - 2.f * slack - 1e-4f - 1e-5f * fabsf(eroot);
   if (lane == 0) out[t] = w;
+}
+__global__ void __launch_bounds__(256) k_walk_tiles(const float4* __restrict__ P, const float4* __restrict__ Q,
+                                                    const float* __restrict__ CE, const int* __restrict__ ID,
+                                                    int ntiles, int size, float slack,
+                                                    const NnRec* __restrict__ nodes, double ox, double oy,
+                                                    WalkTile* __restrict__ out) {
+  // R = node 0's position in the frame (any fixed point gives a valid bound; the root gives a tight one)
+  const float Rx = (float)(nodes[0].x - ox), Ry = (float)(nodes[0].y - oy);
+  const int t = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);  // one wave per tile
+  const int lane = threadIdx.x & 63;
+  if (t >= ntiles) return;
+  walk_tile_bounds(P, Q, CE, ID, t, size, slack, Rx, Ry, lane, out);
+}
+
+// The index of a short node range in ONE launch behind its sort (launch_nn_walk_build_range): block b gathers the
+// 1024 records of super-tile b from the sorted ids (k_walk_gather's records; ID holds the nodes' own ids), scans the
+// run markers into HEAD, and writes the tiles' run records (k_walk_trun), the 32 tile bounds and the super-tile's
+// (walk_tile_bounds).  Runs of equal records are cut at super-tile boundaries: a run's parts are runs too, so the
+// walk's use of them (one key per run, tiles inside a run) holds; it costs one more exact key per cut.
+__global__ void __launch_bounds__(1024) k_walk_range_index(const NnRec* __restrict__ nodes, int n, const int* __restrict__ order,
+                                                           double ox, double oy, float slack, float4* P, float4* Q,
+                                                           float* CE, int* ID, int* HEAD, int2* trun,
+                                                           WalkTile* tiles, WalkTile* supers) {
+  __shared__ int s_h[WALK_TILE * WALK_SUPER];
+  __shared__ int s_id[WALK_TILE * WALK_SUPER];
+  const int t = threadIdx.x;
+  const int b = blockIdx.x;
+  const int j = b * (WALK_TILE * WALK_SUPER) + t;
+  int id = -1, mark = j;
+  float4 pp = make_float4(0.f, 0.f, 1.f, 0.f), qq = pp;
+  float ce = 0.f;
+  if (j < n) {
+    id = order[j];
+    const NnRec& r = nodes[id];
+    pp = make_float4((float)(r.x - ox), (float)(r.y - oy), r.c, r.s);
+    qq = make_float4((float)(r.bx - ox), (float)(r.by - oy), r.ca, r.sa);
+    ce = r.costE;
+    if (t > 0) {
+      const NnRec& o = nodes[order[j - 1]];
+      if (r.x == o.x && r.y == o.y && r.c == o.c && r.s == o.s && r.costE == o.costE) mark = -1;
+    }
+  }
+  P[j] = pp;
+  Q[j] = qq;
+  CE[j] = ce;
+  ID[j] = id;
+  s_h[t] = mark;
+  s_id[t] = id;
+  __syncthreads();
+  for (int d = 1; d < WALK_TILE * WALK_SUPER; d <<= 1) {  // inclusive max-scan of the run markers
+    const int v = t >= d ? s_h[t - d] : -1;
+    __syncthreads();
+    s_h[t] = max(s_h[t], v);
+    __syncthreads();
+  }
+  HEAD[j] = s_h[t];
+  if (t < WALK_SUPER) {
+    const int q0 = t * WALK_TILE;
+    const int h = s_h[q0];
+    int2 tr = make_int2(-1, -1);
+    if (s_h[q0 + WALK_TILE - 1] == h) {
+      int m = 0x7fffffff;
+      for (int q = 0; q < WALK_TILE; q++) m = min(m, s_id[q0 + q]);
+      if (m >= 0) tr = make_int2(h, m);
+    }
+    trun[b * WALK_SUPER + t] = tr;
+  }
+  __syncthreads();  // the block's records are written: bounds from them, one wave per tile, then the super-tile's
+  const float Rx = (float)(nodes[0].x - ox), Ry = (float)(nodes[0].y - oy);
+  const int wv = t >> 6, lane = t & 63;
+  for (int q = wv; q < WALK_SUPER; q += (WALK_TILE * WALK_SUPER) >> 6)
+    walk_tile_bounds(P, Q, CE, ID, b * WALK_SUPER + q, WALK_TILE, slack, Rx, Ry, lane, tiles);
+  if (wv == 0) walk_tile_bounds(P, Q, CE, ID, b, WALK_TILE * WALK_SUPER, slack, Rx, Ry, lane, supers);
 }
 
 // Bounds need no correctly rounded division / square root (the build flag makes '/' and sqrtf
@@ -605,7 +674,10 @@ __device__ __forceinline__ int lc_le(float v) {  // the largest code c with lc_d
 // k_walk_merge takes the 11 smallest (key, node) pairs of the nch partial lists.  Every pair of the
 // sample's true list precedes that 11th entry, each wave's list is exact over its super-tiles, so the
 // merged list equals the walk's (and the brute force's).  Records beyond max_over: the walk goes on.
-template <int FMT, bool SPLIT, bool BRK>
+// SHARE = false (the appended-node search, k_walk_delta): SPLIT's start from (kb, ib) -- there the sample's key cap,
+// (cap, INT_MAX): every pair with key <= cap is kept -- over all super-tiles (nch 1), without the records' shared
+// word; the list goes to pk / pi row o_sp.
+template <int FMT, bool SPLIT, bool BRK, bool SHARE = SPLIT>
 __device__ __forceinline__ void walk_one(const clrrt_sample* __restrict__ S, int B,
                                                     const NnRec* __restrict__ nodes, const float4* __restrict__ P,
                                                     const float4* __restrict__ Q, const float* __restrict__ CE,
@@ -682,7 +754,7 @@ __device__ __forceinline__ void walk_one(const clrrt_sample* __restrict__ S, int
     const float u10 = uni(__shfl(uk, NN_K - 1, 64));
     if (u10 < kth) { kth = u10; idk = 0x7fffffff; }
 #if WALK_SPLIT_SHARE
-    if constexpr (SPLIT) {
+    if constexpr (SPLIT && SHARE) {
       // the record's nch waves share their bounds: each one's 11th entry (or u10, or the handed-over entry) bounds
       // the sample's true 11th key, so a pair above the smallest of them enters no list (a key-only bound, ties
       // kept); published with an ordered-int atomicMin (keys are >= 0) in the record's spare word
@@ -983,7 +1055,7 @@ __device__ __forceinline__ void walk_one(const clrrt_sample* __restrict__ S, int
   auto visit_supers = [&](int la, int lb2, float Tp, float T, bool first) {
     const uint64_t c0 = prof ? __builtin_amdgcn_s_memtime() : 0;
 #if WALK_SPLIT_SHARE
-    if constexpr (SPLIT) refresh();  // the other waves' bounds
+    if constexpr (SPLIT && SHARE) refresh();  // the other waves' bounds
 #endif
     n_sup += 1 + (lb2 >= 0);
     const int sa = gst(la), sb = lb2 >= 0 ? gst(lb2) : -1;
@@ -1121,6 +1193,13 @@ __device__ __forceinline__ void walk_one(const clrrt_sample* __restrict__ S, int
 #define WALK_GROW 2.f
 #endif
   float T = base + WALK_T0, Tp = -__builtin_inff();
+#if CLRRT_DELTA_ONEPASS
+  // the appended-node search with a finite cap: one pass over every tile the cap admits (the cap is the older list's
+  // sort_limit-th key already; passes of growing threshold would only order ~35 tile visits, at a drain per pass)
+  if constexpr (SPLIT && !SHARE) {
+    if (kb < __builtin_inff()) T = __builtin_inff();
+  }
+#endif
   bool budget = !SPLIT && (bud_tiles > 0 || bud_ex > 0);
   for (int pass = 0;; pass++) {
     const float lim_t = fminf(T, kth);
@@ -1752,6 +1831,74 @@ hipError_t launch_nn_walk_search(hipStream_t st, const clrrt_sample* S, int B, c
                        p.sort_limit, cand, ckey, ncand, ctie);
     LAUNCH_CHECK3();
   }
+  return hipSuccess;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The appended-node search of the lag-2 rounds as a walk (option nn_delta_walk): the nodes [first, first + count) two
+// commits appended get a place-ordered index of their own, and every sample walks it from its key cap -- one wave
+// per sample, the bounds, run heads and 64-at-a-time exact keys of the main walk -- instead of k_nn_partial's brute
+// force over every (sample, node) pair.  The list written to pk / pi (NN_K entries per sample, the nodes' own ids:
+// k_nn_merge_delta with nchunks 1, id0 0) holds the first NN_K feasible pairs in (key, id) order among those with
+// key <= cap, as the brute force's chunk lists do after their merge, so the merged lists are the same bit for bit.
+__device__ __forceinline__ float w_dec32(unsigned int u) {
+  return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);  // (clrrt_kernels.hip ord_dec32)
+}
+// (compiled for 4 waves per SIMD, 128 VGPRs: no scratch -- at CLRRT_WALK_WAVES' 96 it spills 64 B/lane -- and it runs
+// in the gap between two rollout kernels, where no 320-register rollout wave needs the room beside it)
+#ifndef CLRRT_DELTA_WAVES
+#define CLRRT_DELTA_WAVES 4
+#endif
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CLRRT_DELTA_WAVES)))
+k_walk_delta(const clrrt_sample* __restrict__ S, int B, const NnRec* __restrict__ nodes, const float4* __restrict__ P,
+             const float4* __restrict__ Q, const float* __restrict__ CE, const int* __restrict__ ID,
+             const int* __restrict__ HEAD, const int2* __restrict__ trun, const WalkTile* __restrict__ tiles, int ntiles,
+             const WalkTile* __restrict__ sup, int nsup, DevParams p, NnFrame fr, const float* __restrict__ seed,
+             unsigned long long* __restrict__ stats, float* __restrict__ pk, int* __restrict__ pi) {
+  const int s = blockIdx.x;
+  if (s >= B) return;
+  const float cap = w_dec32(((const unsigned int*)seed)[s]);
+  walk_one<WALK_FMT_STATE, true, false, false>(S, B, nodes, P, Q, CE, ID, HEAD, trun, tiles, ntiles, sup, nsup, p, fr,
+                                               nullptr, nullptr, nullptr, nullptr, nullptr, stats, 0, 0, nullptr, nullptr,
+                                               0, 1, pk, pi, nsup, s, 0, nsup, cap, 0x7fffffff, s);
+}
+
+int64_t walk_delta_cap(int64_t max_nodes, int64_t max_batch) {
+  // two rounds append at most 2 nodes per sample each, deferred samples add to a commit: larger ranges take the
+  // brute force (launch_nn_delta_walk's caller checks WalkBufs::cap_nodes)
+  return std::min<int64_t>(max_nodes, 6 * max_batch + 1024);
+}
+
+hipError_t launch_nn_delta_walk(hipStream_t st, const clrrt_sample* S, int B, const NnRec* nodes, int first, int count,
+                                const DevParams& p, const NnFrame& fr, double x0, double y0, double x1, double y1,
+                                WalkBufs& w, float* pk, int* pi, const float* ckey, const int* ncand, float* seed,
+                                bool seeded, unsigned long long* stats) {
+  if (count <= 0 || B <= 0) return hipSuccess;
+  if (count > w.cap_nodes) return hipErrorInvalidValue;
+  const int Npad = (count + WALK_TILE * WALK_SUPER - 1) / (WALK_TILE * WALK_SUPER) * (WALK_TILE * WALK_SUPER);
+  const int ntiles = Npad / WALK_TILE, nsup = ntiles / WALK_SUPER;
+  // the keys of launch_nn_walk_build (the search's frame; the order only sets how tight the bounds are)
+  const int kind = w.index_kind;
+  const double hrho = 4.77 * (w.hscale_pct > 0 ? w.hscale_pct : 100) * 0.01;
+  const double span = kind ? fmax(fmax(x1 - x0, y1 - y0), 2.0 * M_PI * hrho) : fmax(x1 - x0, y1 - y0);
+  const double scale = span > 0 ? 65535.0 / span : 1.0;
+  hipLaunchKernelGGL(k_walk_keys, dim3((count + 63) / 64), dim3(64), 0, st, nodes, first + count, x0, y0, scale,
+                     (uint64_t*)w.keys, w.vals, first, kind, hrho);
+  LAUNCH_CHECK3();
+  size_t bytes = w.tmp_bytes;
+  hipError_t e = hipcub::DeviceRadixSort::SortPairs(w.tmp, bytes, (const uint64_t*)w.keys, w.skeys, w.vals, w.sids,
+                                                    count, 0, 64, st);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_walk_range_index, dim3(nsup), dim3(WALK_TILE * WALK_SUPER), 0, st, nodes, count,
+                     (const int*)w.sids, fr.ox, fr.oy, fr.delta, w.P, w.Q, w.CE, w.ID, w.HEAD, w.trun, w.tiles, w.supers);
+  LAUNCH_CHECK3();
+  if (!seeded) {
+    hipLaunchKernelGGL(k_walk_seed, dim3((B + 63) / 64), dim3(64), 0, st, B, p.sort_limit, ckey, ncand, seed);
+    LAUNCH_CHECK3();
+  }
+  hipLaunchKernelGGL(k_walk_delta, dim3(B), dim3(64), 2 * sizeof(float) * (size_t)nsup, st, S, B, nodes, w.P, w.Q, w.CE,
+                     w.ID, w.HEAD, w.trun, w.tiles, ntiles, w.supers, nsup, p, fr, (const float*)seed, stats, pk, pi);
+  LAUNCH_CHECK3();
   return hipSuccess;
 }
 

@@ -513,7 +513,11 @@ int clrrt_walk_audit(clrrt_ctx* ctx, const clrrt_sample* samples, int32_t n, int
 int clrrt_round_sizes(clrrt_ctx* ctx, int64_t* out, int64_t cap, int64_t* n);
 /* Diagnostics: the context's 64 raw work counters (0..2 rollout work, 8..39 search statistics,
  * 40..63 rollout profile counters of a -DCLRRT_ROLL_PROFILE build: 40..47 per-phase clocks, 48..51 wave
- * lifetimes (sum, max), busiest lane's steps, waves, 52..55 queue-drain times and tail steps). */
+ * lifetimes (sum, max), busiest lane's steps, waves, 52..55 queue-drain times and tail steps).
+ * With option "nn_delta_verify" (lag-2 BATCH rounds, a build without the rollout profile): 38 = samples whose
+ * appended-node walk lists were compared with the brute force's, 39 = samples whose NN_K (key bits, id) pairs differ;
+ * 40..43 that walk's super-tile visits, tiles visited, records past the prefilter and exact keys, 50..52 its stage-1
+ * undecided / surely feasible / stage-2 dropped records; 54 / 55 the brute force's queued pairs and exact keys. */
 int clrrt_debug_counters(clrrt_ctx* ctx, int64_t out[64]);
 
 #ifdef __cplusplus

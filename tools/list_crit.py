@@ -1,6 +1,6 @@
 """Where the lists of a lag-2 round come from (rocprofv3 kernel trace of a cfg3 bench): for every gap between two
 rollout kernels on the main stream, the appended-node merge (k_nn_merge_delta) that ended last before the next rollout
-kernel, and before it on its stream the appended-node search (k_nn_partial), and on the walk streams the last main walk
+kernel, and before it on its stream the appended-node search (k_walk_delta or k_nn_partial), and on the walk streams the last main walk
 grid, split launch and split merge that ended before that merge began.  Times in us after the rollout kernel's end.
 Usage: python3 tools/list_crit.py <p_kernel_trace.csv[.gz]>"""
 import bisect
@@ -57,7 +57,9 @@ def main(path):
         f = lambda t: (t - t0) / 1e3
         res["next_rollout"].append(f(t1))
         res["dmerge_end"].append(f(d[1]))
-        p = last_before("k_nn_partial", d[0], stream=d[2], after=roll[i][0] - 5e6)
+        # the appended-node search: the walk over the range's index (k_walk_delta) or the brute force
+        p = max((k for k in (last_before(n, d[0], stream=d[2], after=roll[i][0] - 5e6)
+                             for n in ("k_walk_delta", "k_nn_partial")) if k), key=lambda k: k[1], default=None)
         if p:
             res["partial_start"].append(f(p[0]))
             res["partial_end"].append(f(p[1]))

@@ -61,6 +61,13 @@ _SIGS = {
     "clrrt_round_commit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
     "clrrt_rows_flush": (C.c_int, [C.c_void_p]),
     "clrrt_round_prefetch": (C.c_int, [C.c_void_p, P(abi.Sample), C.c_int32]),
+    # tree-partitioned search: the list pointers may be host or device memory (void* here)
+    "clrrt_nn_range": (C.c_int, [C.c_void_p, P(abi.Sample), C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                                 C.c_void_p]),
+    "clrrt_nn_merge": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_void_p]),
+    "clrrt_round_eval_lists": (C.c_int, [C.c_void_p, P(abi.Sample), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, P(C.c_int32)]),
     "clrrt_simulate": (C.c_int, [C.c_void_p, P(abi.SimCase), C.c_int32, P(abi.RolloutResult), P(C.c_double),
                                  C.c_int32, P(C.c_double), C.c_int32]),
     "clrrt_rollout_batch": (C.c_int, [C.c_void_p, P(abi.RolloutJob), C.c_int32, P(abi.RolloutResult),
@@ -348,6 +355,67 @@ class Planner:
     def rows_flush(self):
         """Write the deferred trajectory rows of the last commit (clrrt_rows_flush)."""
         self._chk(self.L.clrrt_rows_flush(self.h), "rows_flush")
+
+    # tree-partitioned search (include/clrrt.h): list arrays are numpy arrays, or raw device pointers (ints, e.g.
+    # tensor.data_ptr() of a torch tensor on the GPU: no host round trip)
+    @staticmethod
+    def _samples(samples):
+        return samples if isinstance(samples, C.Array) else (abi.Sample * len(samples))(*samples)
+
+    @staticmethod
+    def _list_in(a, dtype, shape):
+        """(pointer, keep-alive) of a list input: an int is a raw pointer, anything else a numpy array of `shape`."""
+        if isinstance(a, int):
+            return C.c_void_p(a), None
+        arr = np.ascontiguousarray(a, dtype=dtype)
+        if arr.shape != shape:
+            raise ValueError(f"list array of shape {arr.shape}, expected {shape}")
+        return C.c_void_p(arr.ctypes.data), arr
+
+    @staticmethod
+    def _lists_out(n, out):
+        """Output lists of n samples: numpy arrays (out None) or the caller's three raw pointers."""
+        if out is not None:
+            ids, keys, cnt = (int(p) for p in out)
+            return (C.c_void_p(ids), C.c_void_p(keys), C.c_void_p(cnt)), out
+        ids = np.full((n, 10), -1, dtype=np.int32)
+        keys = np.full((n, 10), np.inf, dtype=np.float32)
+        cnt = np.zeros(n, dtype=np.int32)
+        return tuple(C.c_void_p(a.ctypes.data) for a in (ids, keys, cnt)), (ids, keys, cnt)
+
+    def nn_range(self, samples, first, count, out=None):
+        """clrrt_nn_range: BATCH-order candidate lists of `samples` over the tree nodes [first, first + count) only.
+        Returns (ids (n, 10) int32, keys (n, 10) float32, counts (n,) int32) -- slots past a count hold -1 / +inf --
+        or, with out = (ids_ptr, keys_ptr, counts_ptr) raw pointers (host or device), writes there and returns out."""
+        arr = self._samples(samples)
+        n = len(arr)
+        ptrs, res = self._lists_out(n, out)
+        self._chk(self.L.clrrt_nn_range(self.h, arr, n, int(first), int(count), *ptrs), "nn_range")
+        return res
+
+    def nn_merge(self, ids, keys, counts, n=None, parts=None, out=None):
+        """clrrt_nn_merge: merges `parts` list sets of the same n samples (ids / keys [parts][n][10], counts
+        [parts][n]: numpy arrays, or raw pointers with n and parts given) in (key, id) order.  Output as nn_range."""
+        if n is None or parts is None:
+            parts, n = np.shape(counts)
+        (pi, ki), (pk, kk), (pc, kc) = (self._list_in(ids, np.int32, (parts, n, 10)),
+                                        self._list_in(keys, np.float32, (parts, n, 10)),
+                                        self._list_in(counts, np.int32, (parts, n)))
+        ptrs, res = self._lists_out(n, out)
+        self._chk(self.L.clrrt_nn_merge(self.h, n, parts, pi, pk, pc, *ptrs), "nn_merge")
+        return res
+
+    def round_eval_lists(self, samples, ids, keys, counts, dev_out_ptr):
+        """clrrt_round_eval_lists: round_eval with the caller's candidate lists (numpy arrays (n, 10) / (n,), or raw
+        pointers) instead of the engine's search; returns the number of records written to dev_out_ptr."""
+        arr = self._samples(samples)
+        n = len(arr)
+        (pi, ki), (pk, kk), (pc, kc) = (self._list_in(ids, np.int32, (n, 10)), self._list_in(keys, np.float32, (n, 10)),
+                                        self._list_in(counts, np.int32, (n,)))
+        n_out = C.c_int32()
+        self._chk(self.L.clrrt_round_eval_lists(self.h, arr, n, pi, pk, pc, C.c_void_p(dev_out_ptr), C.byref(n_out)),
+                  "round_eval_lists")
+        return n_out.value
 
     def simulate_batch(self, jobs, rows=False):
         """jobs: list of (parent, gb, sx, sy).  Returns a list of result dicts (+ rows)."""

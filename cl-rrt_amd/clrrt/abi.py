@@ -21,6 +21,9 @@ ROLL_NAMES = {ROLL_ITERLIMIT: "iterlimit", ROLL_END: "end", ROLL_GOAL: "goal",
               ROLL_COLLISION: "collision", ROLL_ACCLIMIT: "acclimit"}
 REINIT_EMPTY, REINIT_ALL_ERASED, REINIT_COLLISION, REINIT_KEPT = range(4)  # CLRRT_REINIT_*
 CLRRT_WORLD_TO_CAR, CLRRT_CAR_TO_WORLD = 0, 1
+# slots per sample of a candidate list (clrrt_nn_batch, clrrt_nn_range, clrrt_nn_merge, clrrt_round_eval_lists): ids
+# int32 (-1 past the count), keys float32 (+inf past the count), one int32 count per sample for the last three
+LIST_SLOTS = 10
 
 
 class Vehicle(C.Structure):

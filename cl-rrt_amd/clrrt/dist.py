@@ -200,6 +200,93 @@ def shard(n_total, world, rank):
     return first, n_total * (rank + 1) // world - first
 
 
+def node_range(n_nodes, world, rank):
+    """Contiguous node-id range [first, first + count) = [n r / W, n (r + 1) / W) of the tree that `rank` searches in
+    a tree-partitioned round (integer arithmetic, as in `shard`); the ranges of all ranks tile [0, n_nodes)."""
+    first = n_nodes * rank // world
+    return first, n_nodes * (rank + 1) // world - first
+
+
+class PartitionedSearch:
+    """Tree-partitioned nearest-node search of a round (include/clrrt.h): instead of searching the
+    whole replicated tree for its slice of the samples, every rank searches ALL G samples over its `node_range` of
+    the nodes (clrrt_nn_range), one all-gather moves the ranks' lists (10 ids + 10 keys + a count per sample: 84 G
+    bytes per rank), every rank merges them in (key, id) order (clrrt_nn_merge) -- exactly the lists a search of the
+    whole tree returns -- and runs its `shard` slice of the round from its rows of the merged lists
+    (clrrt_round_eval_lists).  The caller then exchanges and commits the records as after clrrt_round_eval
+    (RoundExchange.exchange + Planner.round_commit).  gloo stages the gather through the host, as RoundExchange does.
+
+    The lists stay on the device; the planner's stream must be torch's current stream (Planner.set_stream) or the
+    caller must order the two, as for RoundExchange."""
+
+    K = 10
+    ROW = 4 * (2 * K + 1)  # bytes per sample: ids, keys, count
+
+    def __init__(self, planner, G, device, group=None):
+        if planner.max_batch < G:
+            raise ValueError(f"PartitionedSearch: the planner's max_batch ({planner.max_batch}) must be >= the round's "
+                             f"{G} samples (every rank searches all of them over its node range)")
+        self.pl = planner
+        self.G = int(G)
+        self.group = group
+        self.world = dist.get_world_size(group)
+        self.rank = dist.get_rank(group)
+        self.dev = torch.device(device)
+        self.host = dist.get_backend(group) == "gloo" and self.dev.type != "cpu"
+        K = self.K
+        # this rank's lists in one buffer (one collective): G x 10 ids | G x 10 key bits | G counts, as int32 words
+        self.mine = torch.zeros(self.G * (2 * K + 1), dtype=torch.int32, device=self.dev)
+        # the gathered lists in clrrt_nn_merge's layout [part][sample][10] / [part][sample], and the merged lists
+        self.ids = torch.zeros((self.world, self.G, K), dtype=torch.int32, device=self.dev)
+        self.keys = torch.zeros((self.world, self.G, K), dtype=torch.float32, device=self.dev)
+        self.counts = torch.zeros((self.world, self.G), dtype=torch.int32, device=self.dev)
+        self.m_ids = torch.zeros((self.G, K), dtype=torch.int32, device=self.dev)
+        self.m_keys = torch.zeros((self.G, K), dtype=torch.float32, device=self.dev)
+        self.m_counts = torch.zeros(self.G, dtype=torch.int32, device=self.dev)
+        self.collectives = 0
+        self.bytes_gathered = 0
+
+    def _sync(self):
+        if self.dev.type == "cuda":
+            torch.cuda.current_stream(self.dev).synchronize()
+
+    def lists(self, samples_all):
+        """Steps 1-3: the merged lists of all G samples (device tensors ids (G, 10), keys (G, 10), counts (G,))."""
+        G, K = self.G, self.K
+        if len(samples_all) != G:
+            raise ValueError(f"PartitionedSearch: {len(samples_all)} samples, built for {G}")
+        first, count = node_range(self.pl.size()[0], self.world, self.rank)
+        base = self.mine.data_ptr()
+        self.pl.nn_range(samples_all, first, count, out=(base, base + 4 * G * K, base + 8 * G * K))
+        src = self.mine.cpu() if self.host else self.mine
+        parts = [torch.empty_like(src) for _ in range(self.world)]
+        dist.all_gather(parts, src, group=self.group)
+        self.collectives += 1
+        self.bytes_gathered += self.world * G * self.ROW
+        for r, q in enumerate(parts):
+            q = q.to(self.dev)
+            self.ids[r].copy_(q[:G * K].view(G, K))
+            self.keys[r].copy_(q[G * K:2 * G * K].view(torch.float32).view(G, K))
+            self.counts[r].copy_(q[2 * G * K:])
+        self._sync()  # the engine reads the gathered lists on its own stream
+        self.pl.nn_merge(self.ids.data_ptr(), self.keys.data_ptr(), self.counts.data_ptr(), n=G, parts=self.world,
+                         out=(self.m_ids.data_ptr(), self.m_keys.data_ptr(), self.m_counts.data_ptr()))
+        return self.m_ids, self.m_keys, self.m_counts
+
+    def round_eval(self, samples_all, records_ptr):
+        """One round's evaluate half: searches, gathers and merges the lists of `samples_all` (abi.Sample array of G
+        samples, the same on every rank), then evaluates this rank's `shard` slice from its rows of the merged lists,
+        writing the accepted-node records to records_ptr (e.g. RoundExchange.records_ptr()).  Returns n_local."""
+        from . import abi
+        K = self.K
+        self.lists(samples_all)
+        first, count = shard(self.G, self.world, self.rank)
+        mine = (abi.Sample * count).from_buffer_copy(bytes(samples_all)[first * 24:(first + count) * 24])
+        return self.pl.round_eval_lists(mine, self.m_ids.data_ptr() + 4 * K * first,
+                                        self.m_keys.data_ptr() + 4 * K * first, self.m_counts.data_ptr() + 4 * first,
+                                        records_ptr)
+
+
 def fetch_path_rows(planner, rank, group=None):
     """Complete the committed path's trajectories across ranks (config 5 with N > 1).
 

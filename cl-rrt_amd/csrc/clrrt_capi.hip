@@ -249,6 +249,24 @@ struct clrrt_ctx {
   // (the walk's own statistics go to counters 40..52, the brute force's queued pairs and exact keys to 54 / 55).
   int nn_delta_verify = 0;
   WalkBufs nnw_d{};
+  // Tree-partitioned search (clrrt_nn_range): the walk over a node range [first, first + count) of any size has an
+  // index set of its own (a full set, allocated on first use; launch_nn_walk_build with a node-id base), so the sets
+  // of the pipelined rounds (nnw, nnw_alt, nnw3, nnw_d) stay as they are.  nnr_built: what its index was built for
+  // (n = -1: nothing) -- nodes never change once appended, so it stays valid while the tree size, the range, the frame
+  // and the index options are the same; every call that replaces or drops nodes goes through pf_reset, which clears it.
+  WalkBufs nnw_r{};
+  struct {
+    int64_t n = -1, first = 0, count = 0;
+    double ox, oy, x0, y0, x1, y1;
+    float delta;
+    int kind, hscale;
+  } nnr_built;
+  // clrrt_nn_merge's inputs on the device ([part][sample][CAND_K] ids / keys, [part][sample] counts; grown on demand)
+  int* pm_ids = nullptr;
+  float* pm_keys = nullptr;
+  int* pm_counts = nullptr;
+  int64_t pm_cap = 0;    // (part, sample) pairs the three hold
+  int* d_bad = nullptr;  // [1] clrrt_round_eval_lists: the first sample whose list fails the check
   float* vpk = nullptr;    // nn_delta_verify: the brute force's chunk lists (partial_cap entries) ...
   int* vpi = nullptr;
   float* vseed = nullptr;  // ... and its copy of the caps (k_nn_partial lowers them)
@@ -643,6 +661,14 @@ static void free_all(clrrt_ctx* c) {
     void* wd[] = {d.keys, d.vals, d.tmp, d.P, d.Q, d.CE, d.ID, d.HEAD, d.trun, d.tiles, d.supers, d.skeys, d.sids,
                   c->vpk, c->vpi, c->vseed};
     for (void* p : wd)
+      if (p) hipFree(p);
+  }
+  {
+    WalkBufs& r = c->nnw_r;
+    void* wr[] = {r.keys, r.keys2, r.vals, r.vals2, r.tmp, r.P, r.Q, r.CE, r.ID, r.tiles, r.supers, r.sorder, r.HEAD,
+                  r.ovf_n, r.ovf, r.pk, r.pi, r.skeys, r.sids, r.trun, r.wctr, c->pm_ids, c->pm_keys, c->pm_counts,
+                  c->d_bad};
+    for (void* p : wr)
       if (p) hipFree(p);
   }
   if (c->side) hipStreamSynchronize(c->side);
@@ -1647,10 +1673,15 @@ static bool walk_serves(clrrt_ctx* c, const NnSetup& su) {
 }
 
 // Any tree change other than clrrt_round_commit invalidates a prefetched search.
-static void pf_reset(clrrt_ctx* c) {
+// (pf_discard: the prefetch alone -- the calls that overwrite the list buffers without changing the tree)
+static void pf_discard(clrrt_ctx* c) {
   if (c->pf_state != 0 && c->side) hipStreamSynchronize(c->side);
   c->pf_state = 0;
   c->pf_next.clear();
+}
+static void pf_reset(clrrt_ctx* c) {
+  pf_discard(c);
+  c->nnr_built.n = -1;
   c->nnw_built.n = -1;
   c->nnw.sorted_n = -1;  // the kept sort results describe the old tree
   c->nnw_alt.sorted_n = -1;
@@ -2557,6 +2588,146 @@ int clrrt_round_prefetch(clrrt_ctx* c, const clrrt_sample* next, int32_t n) {
   if (!c || n < 0 || (n > 0 && !next)) return CLRRT_EINVAL;
   if (n > c->cap.max_batch) return fail(c, CLRRT_ECAPACITY, "batch larger than max_batch");
   c->pf_next.assign(next, next + n);
+  return CLRRT_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Tree-partitioned search: a rank searches every sample of the round over its node range only (clrrt_nn_range), the
+// ranks' lists are merged in (key, id) order (clrrt_nn_merge) and the round's rollouts run from the merged lists
+// (clrrt_round_eval_lists).  The three use the context's list buffers (cand, ckey, ncand, ctie) on the main stream.
+static bool range_built_for(const clrrt_ctx* c, const NnSetup& su, int64_t first, int64_t count) {
+  const auto& b = c->nnr_built;
+  return b.n == c->n_nodes && b.first == first && b.count == count && b.ox == su.fr.ox && b.oy == su.fr.oy &&
+         b.delta == su.fr.delta && b.x0 == su.x0 && b.y0 == su.y0 && b.x1 == su.x1 && b.y1 == su.y1 &&
+         b.kind == c->nnw_index && b.hscale == c->nnw_hscale;
+}
+
+// The lists (cand, ckey, ncand) to the caller (host or device memory), after everything queued on the stream.
+static int lists_out(clrrt_ctx* c, int n, int32_t* out_ids, float* out_keys, int32_t* out_n) {
+  HIPC(c, hipMemcpyAsync(out_ids, c->cand, sizeof(int) * CAND_K * n, hipMemcpyDefault, c->stream));
+  HIPC(c, hipMemcpyAsync(out_keys, c->ckey, sizeof(float) * CAND_K * n, hipMemcpyDefault, c->stream));
+  HIPC(c, hipMemcpyAsync(out_n, c->ncand, sizeof(int) * n, hipMemcpyDefault, c->stream));
+  HIPC(c, hipStreamSynchronize(c->stream));
+  return CLRRT_OK;
+}
+
+int clrrt_nn_range(clrrt_ctx* c, const clrrt_sample* samples, int32_t n, int64_t first, int64_t count,
+                   int32_t* out_ids, float* out_keys, int32_t* out_n) {
+  if (!c || n < 0 || (n > 0 && (!samples || !out_ids || !out_keys || !out_n))) return CLRRT_EINVAL;
+  if (first < 0 || count < 0 || first > c->n_nodes || count > c->n_nodes - first)
+    return fail(c, CLRRT_EINVAL, "node range [" + std::to_string(first) + ", " + std::to_string(first) + " + " +
+                                     std::to_string(count) + ") outside the tree's " + std::to_string(c->n_nodes) +
+                                     " nodes");
+  if (n > c->cap.max_batch) return fail(c, CLRRT_ECAPACITY, "batch larger than max_batch");
+  if (n == 0) return CLRRT_OK;
+  pf_discard(c);  // the list buffers are overwritten
+  HIPC(c, hipSetDevice(c->device));
+  hipStream_t st = c->stream;
+  memcpy(c->h_samples, samples, sizeof(clrrt_sample) * n);
+  HIPC(c, hipMemcpyAsync(c->d_samples, c->h_samples, sizeof(clrrt_sample) * n, hipMemcpyHostToDevice, st));
+  c->nn_bf_keys += (int64_t)n * count;
+  c->nn_samples += n;
+  {
+    KTimer kt(c, 0);
+    HIPC(c, hipMemsetAsync(c->ncand, 0, sizeof(int) * n, st));  // count == 0, and the brute force's empty older list
+    const NnSetup su = nn_setup(c);  // the whole tree's frame: the same on every rank
+    if (count > 0 && count >= c->nnw_min_nodes && su.region_ok) {
+      WalkBufs& w = c->nnw_r;
+      const int rc = ensure_walk_set(c, w);
+      if (rc != CLRRT_OK) return rc;
+      if (!range_built_for(c, su, first, count)) {
+        c->nnr_built.n = -1;
+        HIPC(c, launch_nn_walk_build(st, c->nn, (int)count, su.fr, su.x0, su.y0, su.x1, su.y1, w, nullptr, (int)first));
+        auto& b = c->nnr_built;
+        b.n = c->n_nodes; b.first = first; b.count = count;
+        b.ox = su.fr.ox; b.oy = su.fr.oy; b.delta = su.fr.delta;
+        b.x0 = su.x0; b.y0 = su.y0; b.x1 = su.x1; b.y1 = su.y1;
+        b.kind = c->nnw_index; b.hscale = c->nnw_hscale;
+      }
+      c->nn_super_bounds += (int64_t)n * walk_super_count(count);
+      KTimer kt3(c, 3);
+      HIPC(c, launch_nn_walk_search(st, c->d_samples, n, c->nn, (int)count, c->dp, su.fr, su.x0, su.y0, su.x1, su.y1, w,
+                                    c->cand, c->ckey, c->ncand, c->ctie, c->work_ctr + 18, c->nnw_stateless));
+    } else if (count > 0) {
+      // short ranges (and trees the walk does not serve): the brute force's chunk lists over the range, caps from
+      // +inf, merged into the empty list
+      const int max_chunks = (int)std::max<int64_t>(1, c->partial_cap / ((int64_t)n * NN_K));
+      int nch = 0;
+      HIPC(c, launch_nn_delta_partial(st, c->d_samples, n, c->nn, (int)first, (int)count, c->dp, su.fr, c->pk, c->pi,
+                                      max_chunks, nullptr, nullptr, c->nn_seed, false, nullptr, &nch, c->work_ctr + 13));
+      HIPC(c, launch_nn_delta_merge(st, n, nch, c->dp, c->pk, c->pi, (int)first, c->cand, c->ckey, c->ncand, c->ctie));
+    }
+    HIPC(c, launch_nn_lists_check(st, n, c->dp, (int)c->n_nodes, c->cand, c->ckey, c->ncand, c->ctie, nullptr));
+  }
+  return lists_out(c, n, out_ids, out_keys, out_n);
+}
+
+int clrrt_nn_merge(clrrt_ctx* c, int32_t n, int32_t parts, const int32_t* ids, const float* keys, const int32_t* counts,
+                   int32_t* out_ids, float* out_keys, int32_t* out_n) {
+  if (!c || n < 0 || parts < 1 || (n > 0 && (!ids || !keys || !counts || !out_ids || !out_keys || !out_n)))
+    return CLRRT_EINVAL;
+  if (n > c->cap.max_batch) return fail(c, CLRRT_ECAPACITY, "batch larger than max_batch");
+  if (n == 0) return CLRRT_OK;
+  pf_discard(c);  // the list buffers are overwritten
+  HIPC(c, hipSetDevice(c->device));
+  hipStream_t st = c->stream;
+  const int64_t pairs = (int64_t)parts * n;
+  if (pairs > c->pm_cap) {
+    HIPC(c, hipStreamSynchronize(st));
+    for (void* p : {(void*)c->pm_ids, (void*)c->pm_keys, (void*)c->pm_counts})
+      if (p) HIPC(c, hipFree(p));
+    c->pm_ids = nullptr; c->pm_keys = nullptr; c->pm_counts = nullptr;
+    c->pm_cap = 0;
+    HIPC(c, dalloc(&c->pm_ids, pairs * CAND_K));
+    HIPC(c, dalloc(&c->pm_keys, pairs * CAND_K));
+    HIPC(c, dalloc(&c->pm_counts, pairs));
+    c->pm_cap = pairs;
+  }
+  HIPC(c, hipMemcpyAsync(c->pm_ids, ids, sizeof(int) * CAND_K * pairs, hipMemcpyDefault, st));
+  HIPC(c, hipMemcpyAsync(c->pm_keys, keys, sizeof(float) * CAND_K * pairs, hipMemcpyDefault, st));
+  HIPC(c, hipMemcpyAsync(c->pm_counts, counts, sizeof(int) * pairs, hipMemcpyDefault, st));
+  {
+    KTimer kt(c, 0);
+    HIPC(c, launch_nn_merge_parts(st, n, parts, c->dp, c->pm_ids, c->pm_keys, c->pm_counts, c->cand, c->ckey, c->ncand,
+                                  c->ctie));
+  }
+  return lists_out(c, n, out_ids, out_keys, out_n);
+}
+
+int clrrt_round_eval_lists(clrrt_ctx* c, const clrrt_sample* samples, int32_t n, const int32_t* ids, const float* keys,
+                           const int32_t* counts, void* dev_out, int32_t* n_out) {
+  if (!c || n < 0 || !n_out || (n > 0 && (!samples || !ids || !keys || !counts))) return CLRRT_EINVAL;
+  if (n > c->cap.max_batch) return fail(c, CLRRT_ECAPACITY, "batch larger than max_batch");
+  if (c->n_nodes <= 0) return fail(c, CLRRT_ESTATE, "tree not initialised");
+  HIPC(c, hipSetDevice(c->device));
+  *n_out = 0;
+  if (n == 0) return CLRRT_OK;
+  pf_discard(c);  // a prefetched search is for the engine's own lists
+  hipStream_t st = c->stream;
+  if (!c->d_bad) HIPC(c, dalloc(&c->d_bad, 1));
+  memcpy(c->h_samples, samples, sizeof(clrrt_sample) * n);
+  HIPC(c, hipMemcpyAsync(c->d_samples, c->h_samples, sizeof(clrrt_sample) * n, hipMemcpyHostToDevice, st));
+  HIPC(c, hipMemcpyAsync(c->cand, ids, sizeof(int) * CAND_K * n, hipMemcpyDefault, st));
+  HIPC(c, hipMemcpyAsync(c->ckey, keys, sizeof(float) * CAND_K * n, hipMemcpyDefault, st));
+  HIPC(c, hipMemcpyAsync(c->ncand, counts, sizeof(int) * n, hipMemcpyDefault, st));
+  // the lists are checked on the device before any rollout reads them: counts in [0, sort_limit], listed ids inside
+  // the tree (slots past the count become -1, which the rollouts skip)
+  c->h_int[2] = 0x7fffffff;
+  HIPC(c, hipMemcpyAsync(c->d_bad, c->h_int + 2, sizeof(int), hipMemcpyHostToDevice, st));
+  HIPC(c, launch_nn_lists_check(st, n, c->dp, (int)c->n_nodes, c->cand, c->ckey, c->ncand, c->ctie, c->d_bad));
+  HIPC(c, hipMemcpyAsync(c->h_int + 3, c->d_bad, sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPC(c, hipStreamSynchronize(st));
+  if (c->h_int[3] != 0x7fffffff)
+    return fail(c, CLRRT_EINVAL, "candidate list of sample " + std::to_string(c->h_int[3]) +
+                                     ": count outside [0, sort_limit] or a node id outside the tree");
+  int L = n, rc;
+  if ((rc = eval_samples(c, n, false, &L, true)) != CLRRT_OK) return rc;
+  int nn = 0;
+  if ((rc = compact_and_copy(c, L, &nn, false)) != CLRRT_OK) return rc;
+  if (dev_out && nn > 0)
+    HIPC(c, hipMemcpyAsync(dev_out, c->out_nodes, sizeof(clrrt_node) * nn, hipMemcpyDeviceToDevice, st));
+  HIPC(c, hipStreamSynchronize(st));
+  *n_out = nn;
   return CLRRT_OK;
 }
 

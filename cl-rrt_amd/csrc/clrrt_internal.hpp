@@ -241,9 +241,11 @@ int64_t walk_super_count(int64_t n);
 hipError_t launch_nn_walk(hipStream_t st, const clrrt_sample* S, int B, const NnRec* nodes, int N, const DevParams& p,
                           const NnFrame& fr, double x0, double y0, double x1, double y1, WalkBufs& w, int* cand,
                           float* ckey, int* ncand, int* ctie, unsigned long long* stats, bool stateless);
-// launch_nn_walk's two halves: the index of nodes [0, N), then the search of samples over it
+// launch_nn_walk's two halves: the index of nodes [0, N), then the search of samples over it.
+// first > 0 (clrrt_nn_range): the index of the N nodes [first, first + N) alone, holding the nodes' own ids (`nodes`
+// stays the whole tree's array), in the same frame; the search over it takes the same N and is otherwise unchanged.
 hipError_t launch_nn_walk_build(hipStream_t st, const NnRec* nodes, int N, const NnFrame& fr, double x0, double y0,
-                                double x1, double y1, WalkBufs& w, const WalkBufs* prev = nullptr);
+                                double x1, double y1, WalkBufs& w, const WalkBufs* prev = nullptr, int first = 0);
 hipError_t launch_nn_walk_search(hipStream_t st, const clrrt_sample* S, int B, const NnRec* nodes, int N,
                                  const DevParams& p, const NnFrame& fr, double x0, double y0, double x1, double y1,
                                  WalkBufs& w, int* cand, float* ckey, int* ncand, int* ctie, unsigned long long* stats,
@@ -278,6 +280,14 @@ hipError_t launch_nn_delta_partial(hipStream_t st, const clrrt_sample* S, int B,
                                    int* nchunks_out, unsigned long long* tstat = nullptr);
 hipError_t launch_nn_delta_merge(hipStream_t st, int B, int nchunks, const DevParams& p, const float* pk, const int* pi,
                                  int id0, int* cand, float* ckey, int* ncand, int* ctie);
+// Tree-partitioned search: the merge of `parts` list sets of the same B samples (ids / keys [part][sample][10], counts
+// [part][sample]) into a list, and the lists' output format (id -1, key +inf past the count) with, when bad != null,
+// the check of caller-supplied lists (*bad preset to INT_MAX: the smallest sample with a count outside [0, sort_limit]
+// or a listed id outside [0, n_nodes)).
+hipError_t launch_nn_merge_parts(hipStream_t st, int B, int parts, const DevParams& p, const int* ids,
+                                 const float* keys, const int* counts, int* cand, float* ckey, int* ncand, int* ctie);
+hipError_t launch_nn_lists_check(hipStream_t st, int B, const DevParams& p, int n_nodes, int* cand, float* ckey,
+                                 int* ncand, int* ctie, int* bad);
 // Nearest-node search.  exact_scratch != nullptr (EXACT mode, B*N KeyId entries): samples whose
 // selection involves equal keys are re-sorted with the replay of std::sort.  seed: [B] scratch for the
 // chunks' shared key caps (or null).

@@ -3325,4 +3325,123 @@ hipError_t launch_init_root(hipStream_t st, const double* state, clrrt_node* tre
   return hipSuccess;
 }
 
+// --------------------------------------------------------------------------------------------
+// tree-partitioned search (clrrt_nn_range / clrrt_nn_merge / clrrt_round_eval_lists)
+// --------------------------------------------------------------------------------------------
+// Merge of `parts` list sets of the same B samples, ids / keys [part][sample][CAND_K], counts [part][sample] (an
+// all-gather of per-range lists): per sample the first min(limit, valid entries) of the union in (key, id) order
+// (lex_less), in the lists' output format (-1 / +inf past the count).
+// Lane mapping: one wave per 64 consecutive samples.  A part's entries of those samples are one contiguous run of
+// 64 x CAND_K words, so the wave loads it with consecutive lanes on consecutive words (10 fully coalesced loads per
+// array) into LDS rows padded to 11 words, and each lane then reads its own sample's row: lane l, entry j at word
+// 11 l + j -- 11 is odd, so the 32 lanes of an LDS access group fall on 32 different banks.  One lane per sample
+// reading its CAND_K entries straight from memory would touch 20 cache lines per load instruction instead.  The
+// lists go out the same way (rows in LDS, coalesced stores).
+#define MERGE_ROW (CAND_K + 1)
+__global__ void __launch_bounds__(64) k_nn_merge_parts(int B, int parts, int limit, const int* __restrict__ ids,
+                                                       const float* __restrict__ keys, const int* __restrict__ counts,
+                                                       int* __restrict__ cand, float* __restrict__ ckey,
+                                                       int* __restrict__ ncand, int* __restrict__ ctie) {
+  __shared__ int s_i[64 * MERGE_ROW];
+  __shared__ float s_k[64 * MERGE_ROW];
+  const int lane = threadIdx.x;
+  const int s0 = blockIdx.x * 64;
+  const int m = min(64, B - s0);  // samples of this block
+  const int s = s0 + lane;
+  float lk[NN_K];
+  int li[NN_K];
+#pragma unroll
+  for (int j = 0; j < NN_K; j++) { lk[j] = __builtin_inff(); li[j] = 0x7fffffff; }
+  for (int p = 0; p < parts; p++) {
+    const size_t base = ((size_t)p * B + s0) * CAND_K;
+    __syncthreads();  // the previous part's rows are read
+    for (int e = lane; e < m * CAND_K; e += 64) {
+      const int r = e / CAND_K, j = e - r * CAND_K;
+      s_i[r * MERGE_ROW + j] = ids[base + e];
+      s_k[r * MERGE_ROW + j] = keys[base + e];
+    }
+    __syncthreads();
+    if (lane < m) {
+      const int c = min(max(counts[(size_t)p * B + s], 0), CAND_K);
+      for (int j = 0; j < c; j++) {
+        const float k = s_k[lane * MERGE_ROW + j];
+        const int id = s_i[lane * MERGE_ROW + j];
+        if (lex_less(k, id, lk[NN_K - 1], li[NN_K - 1])) topk_insert(lk, li, k, id);
+        else break;  // part lists are sorted
+      }
+    }
+  }
+  int valid = 0;
+#pragma unroll
+  for (int j = 0; j < NN_K; j++) valid += li[j] != 0x7fffffff;
+  const int sel = min(min(limit, valid), CAND_K);
+  int tie = 0;
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < CAND_K; j++) {
+    s_i[lane * MERGE_ROW + j] = j < sel ? li[j] : -1;
+    s_k[lane * MERGE_ROW + j] = j < sel ? lk[j] : __builtin_inff();
+    tie |= (j < sel && j + 1 < valid && lk[j] == lk[j + 1]);
+  }
+  if (lane < m) {
+    ncand[s] = sel;
+    ctie[s] = tie;
+  }
+  __syncthreads();
+  for (int e = lane; e < m * CAND_K; e += 64) {
+    const int r = e / CAND_K, j = e - r * CAND_K;
+    cand[(size_t)s0 * CAND_K + e] = s_i[r * MERGE_ROW + j];
+    ckey[(size_t)s0 * CAND_K + e] = s_k[r * MERGE_ROW + j];
+  }
+}
+
+// Lists in the output format of the partitioned calls: slots past a sample's count hold id -1 (the rollouts skip
+// such a candidate) and key +inf.  With `bad` (clrrt_round_eval_lists: the caller's lists, checked before any
+// rollout reads them): a count outside [0, min(limit, CAND_K)] or one of the first `count` ids outside [0, n_nodes)
+// puts the smallest offending sample into *bad (preset to INT_MAX) and empties that sample's list.
+__global__ void k_nn_lists_check(int B, int limit, int n_nodes, int* __restrict__ cand, float* __restrict__ ckey,
+                                 int* __restrict__ ncand, int* __restrict__ ctie, int* __restrict__ bad) {
+  const int s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= B) return;
+  int c = ncand[s];
+  if (bad) {
+    bool ok = c >= 0 && c <= min(limit, CAND_K);
+    if (ok)
+      for (int j = 0; j < c; j++) {
+        const int id = cand[s * CAND_K + j];
+        ok = ok && id >= 0 && id < n_nodes;
+      }
+    if (!ok) {
+      atomicMin(bad, s);
+      c = 0;
+      ncand[s] = 0;
+    }
+    ctie[s] = 0;
+  }
+  c = min(max(c, 0), CAND_K);
+  for (int j = c; j < CAND_K; j++) {
+    cand[s * CAND_K + j] = -1;
+    ckey[s * CAND_K + j] = __builtin_inff();
+  }
+}
+
+hipError_t launch_nn_merge_parts(hipStream_t st, int B, int parts, const DevParams& p, const int* ids,
+                                 const float* keys, const int* counts, int* cand, float* ckey, int* ncand,
+                                 int* ctie) {
+  if (B <= 0 || parts <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_nn_merge_parts, dim3((B + 63) / 64), dim3(64), 0, st, B, parts, p.sort_limit, ids, keys, counts,
+                     cand, ckey, ncand, ctie);
+  LAUNCH_CHECK();
+  return hipSuccess;
+}
+
+hipError_t launch_nn_lists_check(hipStream_t st, int B, const DevParams& p, int n_nodes, int* cand, float* ckey,
+                                 int* ncand, int* ctie, int* bad) {
+  if (B <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_nn_lists_check, dim3((B + 63) / 64), dim3(64), 0, st, B, p.sort_limit, n_nodes, cand, ckey,
+                     ncand, ctie, bad);
+  LAUNCH_CHECK();
+  return hipSuccess;
+}
+
 }  // namespace clrrt

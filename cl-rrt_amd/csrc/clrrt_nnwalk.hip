@@ -1623,10 +1623,15 @@ hipError_t launch_nn_walk(hipStream_t st, const clrrt_sample* S, int B, const Nn
 // previous round's index): only the appended nodes are keyed and sorted, then merged with it (nodes
 // never change once appended; ties take the older, lower-id entries first, so the order equals a full
 // stable sort's).
+// first > 0: the index of the N nodes [first, first + N) alone (a node range of any size up to the set's capacity,
+// clrrt_nn_range).  Only the key kernel addresses nodes by position: it keys nodes first .. first + N into entries
+// 0 .. N with their own ids as values, and everything after it -- the gather, run heads, tile bounds, and the search --
+// goes through those ids, with `nodes` the whole tree's array (the bounds' fixed point R stays node 0, the root, so
+// every range's bounds are as tight as the whole tree's).  No sort result is kept or reused for a range.
 hipError_t launch_nn_walk_build(hipStream_t st, const NnRec* nodes, int N, const NnFrame& fr, double x0, double y0,
-                                double x1, double y1, WalkBufs& w, const WalkBufs* prev) {
+                                double x1, double y1, WalkBufs& w, const WalkBufs* prev, int first) {
   if (N <= 0) return hipSuccess;
-  if (N > w.cap_nodes) return hipErrorInvalidValue;  // the buffers' shapes (alloc_walk)
+  if (first < 0 || N > w.cap_nodes) return hipErrorInvalidValue;  // the buffers' shapes (alloc_walk)
   const int Npad = (N + WALK_TILE * WALK_SUPER - 1) / (WALK_TILE * WALK_SUPER) * (WALK_TILE * WALK_SUPER);
   const int ntiles = Npad / WALK_TILE, nsup = ntiles / WALK_SUPER;
   const int kind = w.index_kind;
@@ -1638,7 +1643,7 @@ hipError_t launch_nn_walk_build(hipStream_t st, const NnRec* nodes, int N, const
   // (kinds 3 / 4 keep the sector on top: the same scale)
   const double scale = span > 0 ? 65535.0 / span : 1.0;
   hipError_t e;
-  const bool incremental = prev && prev != &w && prev->sorted_n > 0 && prev->sorted_n <= N &&
+  const bool incremental = first == 0 && prev && prev != &w && prev->sorted_n > 0 && prev->sorted_n <= N &&
                            prev->sorted_x0 == x0 && prev->sorted_y0 == y0 && prev->sorted_scale == scale &&
                            prev->sorted_kind == kind;
   if (incremental) {
@@ -1663,15 +1668,15 @@ hipError_t launch_nn_walk_build(hipStream_t st, const NnRec* nodes, int N, const
         return e;
     }
   } else {
-    hipLaunchKernelGGL(k_walk_keys, dim3((N + 63) / 64), dim3(64), 0, st, nodes, N, x0, y0, scale,
-                       (uint64_t*)w.keys, w.vals, 0, kind, hrho);
+    hipLaunchKernelGGL(k_walk_keys, dim3((N + 63) / 64), dim3(64), 0, st, nodes, first + N, x0, y0, scale,
+                       (uint64_t*)w.keys, w.vals, first, kind, hrho);
     LAUNCH_CHECK3();
     size_t bytes = w.tmp_bytes;
     e = hipcub::DeviceRadixSort::SortPairs(w.tmp, bytes, (const uint64_t*)w.keys, w.skeys, w.vals, w.sids, N, 0, 64,
                                            st);
     if (e != hipSuccess) return e;
   }
-  w.sorted_n = N;
+  w.sorted_n = first == 0 ? N : -1;
   w.sorted_x0 = x0;
   w.sorted_y0 = y0;
   w.sorted_scale = scale;

@@ -369,6 +369,46 @@ int clrrt_round_prefetch(clrrt_ctx* ctx, const clrrt_sample* next_samples, int32
  * (clrrt_set_obstacles, clrrt_set_params) does it first; a round-API caller ends a query with it. */
 int clrrt_rows_flush(clrrt_ctx* ctx);
 
+/* ---- tree-partitioned nearest-node search (engine extension, no reference counterpart) ----
+ * A sharded round in which every rank searches the whole replicated tree pays the search W times over.  Instead rank
+ * r searches ALL samples of the round over only its 1/W of the nodes (clrrt_nn_range over a contiguous id range), the
+ * ranks all-gather their per-sample lists (10 ids + 10 keys + a count per sample and rank: 84 bytes), every rank
+ * merges them (clrrt_nn_merge) and runs its slice of the round from the merged lists (clrrt_round_eval_lists), then
+ * exchanges and commits the records as after clrrt_round_eval.  Lists are ordered by the total order (key, node id)
+ * of CLRRT_MODE_BATCH; the ranges are disjoint and each part list is its range's first sort_limit entries, so the
+ * merge over ranges that cover [0, tree size) is exactly the list clrrt_nn_batch(..., CLRRT_MODE_BATCH) returns and
+ * the round grows the same tree bit for bit.
+ * Common to the three calls: list arrays hold 10 slots per sample (slots past a sample's count: id -1, key +inf);
+ * the list pointers (ids, keys, counts, out_*) may be host or device memory and are copied on the context's stream;
+ * `samples` is a host array; each call returns after its results are complete; CLRRT_EINVAL for a null pointer with
+ * n > 0, CLRRT_ECAPACITY for n > max_batch, n == 0 does nothing.  A search prefetched with clrrt_round_prefetch is
+ * discarded (the calls use the context's list buffers).  The searches count in clrrt_search_work and time under
+ * clrrt_kernel_time families 0 and 3 like the engine's own. */
+/* Engine extension, no reference counterpart: BATCH-order candidate lists of samples[0 .. n) over the tree nodes
+ * [first, first + count) ONLY: per sample the first min(sort_limit, feasible nodes of the range) nodes of the range
+ * that pass feasibleNode, ascending in (key, node id), with the nodes' own (global) ids -- the list
+ * clrrt_nn_batch(..., CLRRT_MODE_BATCH) would return over a tree holding only those nodes.  count == 0 gives empty
+ * lists.  The Morton frame and float frame are the whole tree's, so every rank uses the same.  A range of at least
+ * "nn_walk_min" nodes takes the walk search over an index of the range (kept while the tree, the range and the
+ * frame are unchanged; the options "nn_walk_stateless", "nn_walk_budget_tiles" / "_keys" and "nn_walk_index" apply as
+ * to the main search), a shorter one the brute force.  CLRRT_EINVAL for first < 0, count < 0 or
+ * first + count > tree size. */
+int clrrt_nn_range(clrrt_ctx* ctx, const clrrt_sample* samples, int32_t n, int64_t first, int64_t count,
+                   int32_t* out_ids, float* out_keys, int32_t* out_n);
+/* Engine extension, no reference counterpart: merges `parts` list sets of the same n samples -- ids and keys laid out
+ * [part][sample][10], counts [part][sample], what an all-gather of clrrt_nn_range outputs produces -- into one: per
+ * sample the first min(sort_limit, valid entries) of the union in (key, id) order.  Part lists must be ascending in
+ * that order (clrrt_nn_range's are); counts are clamped to [0, 10].  CLRRT_EINVAL for parts < 1. */
+int clrrt_nn_merge(clrrt_ctx* ctx, int32_t n, int32_t parts, const int32_t* ids, const float* keys,
+                   const int32_t* counts, int32_t* out_ids, float* out_keys, int32_t* out_n);
+/* Engine extension, no reference counterpart: clrrt_round_eval (BATCH semantics) with the caller's candidate lists
+ * instead of the engine's search: sample i tries the nodes ids[10 i .. 10 i + counts[i]) in order.  The lists are
+ * checked on the device before any rollout reads them -- counts in [0, sort_limit], the listed ids in [0, tree size)
+ * -- and a violation returns CLRRT_EINVAL with the offending sample in clrrt_last_error, the tree and the counters
+ * unchanged.  dev_out / n_out as for clrrt_round_eval; clrrt_round_commit follows as usual. */
+int clrrt_round_eval_lists(clrrt_ctx* ctx, const clrrt_sample* samples, int32_t n, const int32_t* ids,
+                           const float* keys, const int32_t* counts, void* dev_out, int32_t* n_out);
+
 /* checkObsDistance(const vector<double>& x) (rrt/include/rrt/collision.h:41, the documented collision
  * hook README.md:40-47): out[i] = the distance the context's collision mode gives for states[i] (10
  * doubles: x, y, theta, ..., t in column 6) — 100 under CLRRT_COLLISION_STUB

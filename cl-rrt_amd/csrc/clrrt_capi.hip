@@ -149,7 +149,8 @@ struct clrrt_ctx {
   int n_cu = 256;
   int* roll_q = nullptr;      // [1] queue head
   int* roll_best = nullptr;   // [max_batch] first successful candidate per sample
-  int roll_priority = 1;      // option "roll_priority": likely-long rollouts first (k_roll_order)
+  int roll_priority = 1;      // option "roll_priority": longest-predicted chains first (k_roll_order)
+  int roll_order_verify = 0;  // option "roll_order_verify" (diagnostics): check the order, work counters 6 / 7
   int roll_coop = 1;          // option "roll_coop": wave-cooperative collision checks in k_roll_run
   int roll_spread = 1;        // option "roll_spread": a short queue is spread over the persistent waves
   int roll_lanes = 0;         // option "roll_lanes": lanes per wave that take jobs (0: 64, or fewer by roll_spread)
@@ -184,7 +185,7 @@ struct clrrt_ctx {
   // window without a result
   int64_t ex_stats[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   int* roll_perm = nullptr;   // [max_batch * CAND_K] queue order
-  int* roll_pflag = nullptr;  // [2 max_batch * CAND_K + scratch] flags, scan positions, scan scratch
+  int* roll_pflag = nullptr;  // [roll_order_ints(max_batch * CAND_K)] length classes, block histograms, verify marks
   // extractBestPath scratch (allocated on first use, max_nodes entries each)
   GoalRec* goal_recs = nullptr;
   int* bp_path = nullptr;  // [max_nodes + 2]: chain, then count and length
@@ -757,7 +758,7 @@ int clrrt_create(const clrrt_params* p, const clrrt_capacity* cap, int device, c
   chk(dalloc(&c->roll_q, 1));
   chk(dalloc(&c->roll_best, B));
   chk(dalloc(&c->roll_perm, (int64_t)B * CAND_K));
-  chk(dalloc(&c->roll_pflag, 2 * (int64_t)B * CAND_K + (int64_t)(roll_order_scratch_bytes(B * CAND_K) / 4 + 64)));
+  chk(dalloc(&c->roll_pflag, (int64_t)roll_order_ints((int)(B * CAND_K))));
   {
     int ncu = 0;
     if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && ncu > 0)
@@ -1469,6 +1470,7 @@ int clrrt_set_option(clrrt_ctx* c, const char* key, int64_t value) {
   else if (k == "roll_blocks" && value >= 0 && value < (1 << 20)) c->roll_blocks = (int)value;
   else if (k == "nn_pipeline") c->nn_pipeline = value != 0;
   else if (k == "roll_priority") c->roll_priority = value != 0;
+  else if (k == "roll_order_verify") c->roll_order_verify = value != 0;  // diagnostics: counters 6 / 7
   else if (k == "roll_coop") c->roll_coop = value != 0;
   else if (k == "roll_spread") c->roll_spread = value != 0;
   else if (k == "roll_lanes") c->roll_lanes = (int)std::max<int64_t>(0, std::min<int64_t>(64, value));
@@ -2092,11 +2094,13 @@ static int eval_samples(clrrt_ctx* c, int n, bool exact, int* L_out, bool have_l
     // persistent blocks (1 resident per CU: the step loop fills the register file).  The rollout kernel's
     // makespan is its longest chains, not its width, while the side stream's search of the next round
     // grows with the tree and takes the CUs the rollouts leave; so the grid narrows as the tree grows:
-    // 7/8 of the CUs below 300 k nodes, 5/8 to 700 k, 1/2 to 1.1 M, 3/8 beyond (cfg3 round time by tree
+    // 7/8 of the CUs below 300 k nodes, 5/8 to 700 k, 1/2 to 1.1 M, 1/4 beyond (cfg3 round time by tree
     // size and width, tools/blocks_vs_size.py: each step the best or within 2% of it; a fixed 5/8 grid
-    // was the best single width).  Scheduling only: results do not depend on the width.
+    // was the best single width; the last step was 3/8 until round 8: with the queue served by length class
+    // 1/4 measured +1.55% over 3/8, three runs each, and wider schedules lower, profiles/r08a_cfg3_control.txt,
+    // r08a_cfg3_widths.txt).  Scheduling only: results do not depend on the width.
     const int64_t nt = c->n_nodes;
-    const int eighths = nt < 300000 ? 7 : nt < 700000 ? 5 : nt < 1100000 ? 4 : 3;
+    const int eighths = nt < 300000 ? 7 : nt < 700000 ? 5 : nt < 1100000 ? 4 : 2;
     const int blocks = c->roll_blocks > 0 ? std::min(c->roll_blocks, 4 * c->n_cu)
                        : c->cu_split > 0  ? std::max(1, (c->cu_split * c->n_cu) / 8)
                                           : std::max(1, (eighths * c->n_cu) / 8);
@@ -2105,6 +2109,7 @@ static int eval_samples(clrrt_ctx* c, int n, bool exact, int* L_out, bool have_l
     if (c->roll_priority) {
       a.perm = c->roll_perm;
       a.pflag = c->roll_pflag;
+      a.order_verify = c->roll_order_verify;
     }
     unsigned long long*& dbg_host = c->dbg_host;  // diagnostics heartbeat (host-mapped)
     if (c->debug_sync) {  // diagnostics: which kernel of the round does not finish

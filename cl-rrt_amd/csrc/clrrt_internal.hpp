@@ -104,11 +104,12 @@ struct RollArgs {
   RollRes* __restrict__ res_gb;            // SPEC: goal-biased rollout (outcome -1 = not run)
   unsigned long long* ctr;  // [3] steps, scan points, box tests (nullable)
   int njobs;
-  // persistent rollouts: queue order (nullable).  k_roll_flag flags the jobs likely to run long
-  // (pflag[q], q = k B + s), the queue serves them first (perm[position] = q); results do not depend
-  // on the order
+  // persistent rollouts: queue order (nullable).  k_roll_flag writes each job's predicted length class
+  // (pflag[q], q = k B + s), the queue serves the classes in descending order (perm[position] = q); results
+  // do not depend on the order.  order_verify: k_roll_order_check after them (work counters 6 / 7)
   int* perm;
   int* pflag;
+  int order_verify;
   int B;
   int coop_off;     // k_roll_run's cooperative collision scratch: byte offset in the dynamic LDS
   int coop_enable;  // option "roll_coop": use it where it applies (launch_rollout_persistent)
@@ -320,7 +321,7 @@ struct FillInts {
   }
 };
 hipError_t launch_fill_ints(hipStream_t st, const FillInts& f);
-size_t roll_order_scratch_bytes(int n);  // k_roll_order's scan scratch for n jobs
+size_t roll_order_ints(int n);  // ints of RollArgs::pflag's buffer for n jobs
 size_t replay_bytes();
 size_t carry_bytes();  // one suspended rollout (deferred samples)
 // deferred rows: the committed rollouts' start states (jobs/recs from launch_compact, prep and res of the

@@ -1482,39 +1482,155 @@ struct Carry {
 
 size_t carry_bytes() { return sizeof(Carry); }
 
-// Scheduling only: a rollout toward a sample 8-20 m away (1.7-4.2 turning radii) at 30-90 degrees off
-// the heading is the kind that ends in the iteration limit after the full horizon (the vehicle
-// circles without reaching the reference: tools/orbit_predict.py, cfg3 round 40: this class is 3% of
-// the jobs and holds 472 of the 501 jobs of >= 300 steps).  Served first, these chains no longer
-// start late and set the kernel's makespan.
-__device__ __forceinline__ int roll_likely_long(const double* st, double sx, double sy) {
-  const float dx = (float)(sx - st[0]), dy = (float)(sy - st[1]);
-  const float d2 = dx * dx + dy * dy;
-  if (!(d2 >= 64.f && d2 < 400.f)) return 0;
-  const float c = cosf((float)st[2]), s = sinf((float)st[2]);
-  const float along = dx * c + dy * s, across = fabsf(dy * c - dx * s);
+// Queue order by predicted chain length (option roll_priority; scheduling only, results do not depend on it).  With
+// a cap of T steps per launch (defer_steps) every wave's last refill sets its tail: one chain of >= 60 steps among
+// short ones leaves the other lanes idle for the rest of the launch.  Each job gets a length class c in
+// [0, ROLL_NB) from what is known before it runs; the queue serves the classes in descending order and keeps the
+// k-major order q = k B + s within a class.  What the classes are built from (tools/roll_order_predict.py,
+// profiles/r08a_roll_order_step0.txt; cfg3, T = 128):
+//   heavy-tailed chains: a moving parent.  Nine in ten end within a step or two (an early collision, the sample
+//     reached), 2-3% run >= 60 steps (a late collision, a long goal-biased follow-up) and nothing known beforehand
+//     tells which, so they start before the steady chains: none of the long ones starts late.
+//   steady chains: a parent at rest (the root and its zero-length children) accelerates for ~60 steps before anything
+//     can end its rollout and runs ~75 steps with little spread; served together they end together, so a wave's
+//     lanes go idle together.  Straight ahead (< 10 degrees) 15-20% run >= 100 steps, so those go first.
+//   chains likely to reach the cap: an orbit (roll_orbit_class), and a standing start toward a sample under 7 m
+//     away or >= 45 degrees off the heading (35-70% run >= 100 steps).  60-90% of those standing starts succeed, so
+//     their first candidate is served at the front and the others after the first half's steady chains, when
+//     they are skipped at fetch.
+//   halves: all ten candidates of a sample are alike (a sample's list is of moving or of resting nodes), and a class
+//     that holds them all runs them side by side -- the later ones no longer find the earlier one's success at fetch
+//     (rollout lane-steps +8% when tried).  So the classes are formed per half of the candidate list: by the time
+//     candidates 5-9 of a steady sample are fetched, candidates 0-4 have ended.
+//   7  first half: heavy-tailed; orbits; candidate 0 of a standing start likely to reach the cap
+//   6, 5  first half: steady, straight ahead / the rest
+//   4  candidates 1-9 of a standing start likely to reach the cap
+//   3  second half: heavy-tailed
+//   2, 1  second half: steady, straight ahead / the rest
+//   0  no candidate (skipped at fetch)
+// In the queue model an order by expected length alone (a least-squares fit, 8 geometric classes) moved 3% of the
+// wave-steps, this one 15%, perfect longest-first 20%.
+constexpr int ROLL_NB = 8;
+
+// A rollout toward a sample 8-20 m away (1.7-4.2 turning radii) at 30-90 degrees off the heading is the kind that
+// ends in the iteration limit after the full horizon (the vehicle circles without reaching the reference:
+// tools/orbit_predict.py, cfg3 round 40: this class is 3% of the jobs and holds 472 of the 501 jobs of >= 300 steps).
+__device__ __forceinline__ bool roll_orbit_class(float d2, float along, float across) {
+  if (!(d2 >= 64.f && d2 < 400.f)) return false;
   // 30 <= angle < 90 degrees: along > 0 and across >= tan(30 deg) along
-  return (along > 0.f && across >= 0.57735f * along) ? 1 : 0;
+  return along > 0.f && across >= 0.57735f * along;
 }
 
-// Queue order: flagged positions first (in q order), then the rest (in q order).
-__global__ void __launch_bounds__(256) k_roll_order(const int* __restrict__ pflag, const int* __restrict__ ppos,
-                                                    int n, int* __restrict__ perm) {
+// Length class of candidate k's rollout from node state st toward (sx, sy) in a launch whose chains run at most
+// `scale` steps (the cap T, or the horizon without deferral).
+__device__ __forceinline__ int roll_length_class(const double* st, double sx, double sy, int k, float scale) {
+  const float dx = (float)(sx - st[0]), dy = (float)(sy - st[1]);
+  const float d2 = dx * dx + dy * dy;
+  const float c = cosf((float)st[2]), s = sinf((float)st[2]);
+  const float along = dx * c + dy * s, across = fabsf(dy * c - dx * s);
+  const bool first_half = k < CAND_K / 2;
+  if ((float)st[4] >= 0.5f) return (first_half || roll_orbit_class(d2, along, across)) ? 7 : 3;
+  // a standing start: predicted chain steps (128: under 7 m or >= 45 degrees; 100: < 10 degrees; else 75)
+  const float pred = (d2 < 49.f || across >= along) ? 128.f : across < 0.17633f * along ? 100.f : 75.f;
+  if (pred >= scale) return k == 0 ? 7 : 4;
+  if (pred >= 0.70710678f * scale) return first_half ? 6 : 2;
+  return first_half ? 5 : 1;
+}
+
+// Length classes (roll_priority): cls[q] for queue position q = k B + s, and the block's class histogram
+// hist[block][ROLL_NB] for k_roll_order.  256 threads per block.
+__global__ void __launch_bounds__(256) k_roll_flag(RollArgs a, int* __restrict__ hist) {
+  __shared__ int s_h[ROLL_NB];
+  if (threadIdx.x < ROLL_NB) s_h[threadIdx.x] = 0;
+  __syncthreads();
   const int q = blockIdx.x * blockDim.x + threadIdx.x;
-  if (q >= n) return;
-  const int nf = ppos[n - 1] + pflag[n - 1];
-  const int pos = pflag[q] ? ppos[q] : nf + (q - ppos[q]);
+  int c = -1;
+  if (q < a.njobs) {
+    const int k = q / a.B, s = q - k * a.B;
+    const int id = a.cand[s * CAND_K + k];
+    c = 0;
+    if (id >= 0) {
+      const float scale = (float)(a.cap > 0 ? a.cap : a.p.n_steps_max);
+      c = roll_length_class(a.tree[id].state, a.samples[s].x, a.samples[s].y, k, scale);
+    }
+    a.pflag[q] = c;
+  }
+#pragma unroll
+  for (int cc = 0; cc < ROLL_NB; cc++) {
+    const uint64_t b = __ballot(c == cc);
+    if ((threadIdx.x & 63) == 0 && b) atomicAdd(&s_h[cc], __popcll(b));
+  }
+  __syncthreads();
+  if (threadIdx.x < ROLL_NB) hist[blockIdx.x * ROLL_NB + threadIdx.x] = s_h[threadIdx.x];
+}
+
+// Queue order: a stable partition of the positions by class, descending (perm[position] = q).  Block b places its
+// 256 positions: a class's base is the count of all higher classes plus the class's count in the blocks before b
+// (from k_roll_flag's nblk block histograms), then the rank within the block.
+// Every block reads all nblk x ROLL_NB histogram entries, so the launch's work is O(nblk^2): 640 blocks x 5120 ints at
+// 16384 samples (8 us); a much larger batch wants a scan of the histograms between the two kernels instead.
+__global__ void __launch_bounds__(256) k_roll_order(const int* __restrict__ cls, const int* __restrict__ hist, int n,
+                                                    int nblk, int* __restrict__ perm) {
+  __shared__ int s_tot[ROLL_NB], s_pre[ROLL_NB], s_w[4][ROLL_NB];
+  if (threadIdx.x < ROLL_NB) s_tot[threadIdx.x] = s_pre[threadIdx.x] = 0;
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  {
+    // thread t sums class t % ROLL_NB over the blocks t / ROLL_NB, + 256 / ROLL_NB, ...
+    const int cc = threadIdx.x % ROLL_NB;
+    int tot = 0, pre = 0;
+    for (int b = threadIdx.x / ROLL_NB; b < nblk; b += 256 / ROLL_NB) {
+      const int h = hist[b * ROLL_NB + cc];
+      tot += h;
+      pre += b < (int)blockIdx.x ? h : 0;
+    }
+    if (tot) atomicAdd(&s_tot[cc], tot);
+    if (pre) atomicAdd(&s_pre[cc], pre);
+  }
+  const int q = blockIdx.x * blockDim.x + threadIdx.x;
+  const int c = q < n ? cls[q] : -1;
+  int rank = 0;
+#pragma unroll
+  for (int cc = 0; cc < ROLL_NB; cc++) {
+    const uint64_t b = __ballot(c == cc);
+    if (lane == 0) s_w[wv][cc] = __popcll(b);
+    if (c == cc) rank = __popcll(b & ((1ull << lane) - 1));
+  }
+  __syncthreads();
+  if (c < 0) return;
+  int pos = s_pre[c] + rank;
+  for (int cc = c + 1; cc < ROLL_NB; cc++) pos += s_tot[cc];
+  for (int w = 0; w < wv; w++) pos += s_w[w][c];
   perm[pos] = q;
 }
 
-// Queue order flags (roll_priority): pflag[q] for queue position q = k B + s, 1 for the jobs likely to run
-// the whole horizon (roll_likely_long); k_roll_order then serves them first.
-__global__ void __launch_bounds__(256) k_roll_flag(RollArgs a) {
-  const int j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= a.njobs) return;
-  const int id = a.cand[j];
-  a.pflag[(j % CAND_K) * a.B + j / CAND_K] =
-      id < 0 ? 0 : roll_likely_long(a.tree[id].state, a.samples[j / CAND_K].x, a.samples[j / CAND_K].y);
+// Diagnostics (option roll_order_verify): perm is a permutation of [0, n) -- mark[] zeroed by the caller counts the
+// visits of each q --, classes do not increase along the queue and q ascends within a class.  Work counter 6 counts
+// the positions checked, 7 the positions wrong.
+__global__ void __launch_bounds__(256) k_roll_order_check(const int* __restrict__ perm, const int* __restrict__ cls,
+                                                          int* __restrict__ mark, int n, unsigned long long* ctr) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  bool bad = false;
+  if (i < n) {
+    const int q = perm[i];
+    bad = q < 0 || q >= n;
+    if (!bad) {
+      bad = atomicAdd(&mark[q], 1) != 0;
+      if (i + 1 < n) {
+        const int q2 = perm[i + 1];
+        if (q2 >= 0 && q2 < n) {
+          const int c1 = cls[q], c2 = cls[q2];
+          bad = bad || c1 < c2 || (c1 == c2 && q >= q2);
+        }
+      }
+      bad = bad || cls[q] < 0 || cls[q] >= ROLL_NB;
+    }
+  }
+  const uint64_t bc = __ballot(i < n), bb = __ballot(bad);
+  if ((threadIdx.x & 63) == 0 && ctr) {
+    if (bc) atomicAdd(&ctr[6], (unsigned long long)__popcll(bc));
+    if (bb) atomicAdd(&ctr[7], (unsigned long long)__popcll(bb));
+  }
 }
 
 #ifndef REFILL_MIN
@@ -3024,21 +3140,20 @@ static hipError_t launch_roll_t(hipStream_t st, const RollArgs& a) {
   return hipSuccess;
 }
 
-// The queue order from k_roll_flag's flags: perm = flagged positions, then the others (both ascending).
-// a.pflag's buffer holds [njobs flags][njobs exclusive-scan positions][scan scratch].
-size_t roll_order_scratch_bytes(int n) {
-  size_t bytes = 0;
-  hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, (const int*)nullptr, (int*)nullptr, n);
-  return bytes;
-}
+// The queue order: a.pflag's buffer holds [njobs classes][block histograms][njobs marks of roll_order_verify].
+size_t roll_order_ints(int n) { return 2 * (size_t)n + (size_t)((n + 255) / 256) * ROLL_NB + 64; }
 static hipError_t roll_order(hipStream_t st, const RollArgs& a) {
   if (!a.perm || !a.pflag) return hipSuccess;
-  int* ppos = a.pflag + a.njobs;
-  void* tmp = (void*)(((uintptr_t)(a.pflag + 2 * (size_t)a.njobs) + 255) & ~(uintptr_t)255);  // 256 B spare
-  size_t bytes = roll_order_scratch_bytes(a.njobs);
-  hipError_t e = hipcub::DeviceScan::ExclusiveSum(tmp, bytes, a.pflag, ppos, a.njobs, st);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_roll_order, dim3((a.njobs + 63) / 64), dim3(64), 0, st, a.pflag, ppos, a.njobs, a.perm);
+  const int nblk = (a.njobs + 255) / 256;
+  int* hist = a.pflag + a.njobs;
+  hipLaunchKernelGGL(k_roll_flag, dim3(nblk), dim3(256), 0, st, a, hist);
+  hipLaunchKernelGGL(k_roll_order, dim3(nblk), dim3(256), 0, st, a.pflag, hist, a.njobs, nblk, a.perm);
+  if (a.order_verify) {
+    int* mark = hist + (size_t)nblk * ROLL_NB;
+    hipError_t e = hipMemsetAsync(mark, 0, sizeof(int) * (size_t)a.njobs, st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_roll_order_check, dim3(nblk), dim3(256), 0, st, a.perm, a.pflag, mark, a.njobs, a.ctr);
+  }
   return hipGetLastError();
 }
 
@@ -3092,10 +3207,13 @@ hipError_t launch_rollout_persistent(hipStream_t st, const RollArgs& a0, int B, 
   }
   a.lanes_per_wave = lpw;
   const int nb = blocks < (nqueue + 4 * lpw - 1) / (4 * lpw) ? blocks : (nqueue + 4 * lpw - 1) / (4 * lpw);
-  if (a.njobs > 0 && a.perm && a.pflag) {  // queue order: the likely-long jobs first
-    hipLaunchKernelGGL(k_roll_flag, dim3((a.njobs + 63) / 64), dim3(64), 0, st, a);
-    LAUNCH_CHECK();
+  // queue order by length class -- for a round with more jobs than the grid has lanes.  Fewer start almost at once
+  // (behind the carried chains and the replays, which are not ordered), so no order shortens the launch, and the
+  // classes would pack the long standing starts into the same waves (cfg2, 40960 jobs on 57344 lanes: the launch 5%
+  // longer in three pairs of three).  roll_order_verify builds and checks the order for every queue.
+  if (a.njobs > 0 && a.perm && a.pflag && (a.order_verify || a.njobs > 256 * blocks)) {
     if ((e = roll_order(st, a)) != hipSuccess) return e;
+    LAUNCH_CHECK();
   } else {
     a.perm = nullptr;
   }

@@ -519,7 +519,9 @@ int clrrt_enable_timing(clrrt_ctx* ctx, int32_t on);
  * walk search, default 8192; below it the brute force), "nn_walk_stateless", "nn_walk_budget_tiles",
  * "nn_walk_budget_keys", "nn_walk_chunks", "nn_walk_max_over", "nn_walk_half_max", "nn_walk_waves", "nn_walk_lds_floor", "nn_walk_double", "nn_pipeline",
  * "nn_lag" (0: by query length, 1, 2), "nn_exact_fused", "nn_debug" (diagnostics; changes results),
- * "roll_priority", "roll_coop", "roll_spread", "roll_lanes", "rows_deferred", "exact_min_width",
+ * "roll_priority" (1: a round of more rollout jobs than the grid has lanes is served by predicted length class,
+ * default; 0: plain order), "roll_order_verify" (diagnostics), "roll_coop", "roll_spread", "roll_lanes",
+ * "rows_deferred", "exact_min_width",
  * "cu_split", "walk_cu_reserve", "stream_prio", "side_priority" (see clrrt_capi.hip). */
 int clrrt_set_option(clrrt_ctx* ctx, const char* key, int64_t value);
 /* Nearest-node search diagnostics since the last clrrt_reset_counters.  out[0..6] unused (0).  Brute
@@ -557,7 +559,10 @@ int clrrt_round_sizes(clrrt_ctx* ctx, int64_t* out, int64_t cap, int64_t* n);
  * With option "nn_delta_verify" (lag-2 BATCH rounds, a build without the rollout profile): 38 = samples whose
  * appended-node walk lists were compared with the brute force's, 39 = samples whose NN_K (key bits, id) pairs differ;
  * 40..43 that walk's super-tile visits, tiles visited, records past the prefilter and exact keys, 50..52 its stage-1
- * undecided / surely feasible / stage-2 dropped records; 54 / 55 the brute force's queued pairs and exact keys. */
+ * undecided / surely feasible / stage-2 dropped records; 54 / 55 the brute force's queued pairs and exact keys.
+ * With option "roll_order_verify" (persistent rollouts with "roll_priority" 1): 6 = rollout queue positions checked
+ * (the order is a permutation of the round's jobs, length classes do not increase along it, positions ascend within
+ * a class), 7 = positions wrong. */
 int clrrt_debug_counters(clrrt_ctx* ctx, int64_t out[64]);
 
 #ifdef __cplusplus

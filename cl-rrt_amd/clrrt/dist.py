@@ -170,6 +170,111 @@ class ShardExchange:
         return self.rx.collectives
 
 
+_xlib = None
+
+
+def xchg_lib():
+    """libclrrt_xchg.so (include/clrrt_xchg.h), loaded after libclrrt.so (raises loudly when it has not been built)."""
+    global _xlib
+    if _xlib is None:
+        import ctypes as C
+        import os
+        from . import EXCHANGE_FN, PKG_DIR, abi, lib
+        lib()  # libclrrt.so first (and, through it, the one HIP runtime of the process)
+        L = C.CDLL(os.path.join(PKG_DIR, "libclrrt_xchg.so"))
+        P = C.POINTER
+        sigs = {
+            "clrrt_xchg_last_error": (C.c_char_p, []),
+            "clrrt_xchg_unique_id": (C.c_int, [C.c_void_p]),
+            "clrrt_xchg_create_rccl": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                 P(C.c_void_p)]),
+            "clrrt_xchg_group_create": (C.c_int, [C.c_int32, C.c_int32, P(C.c_void_p)]),
+            "clrrt_xchg_group_destroy": (None, [C.c_void_p]),
+            "clrrt_xchg_create_local": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                  P(C.c_void_p)]),
+            "clrrt_xchg_hook": (C.c_int32, [C.c_void_p, P(abi.ExchangeIO)]),
+            "clrrt_xchg_attach": (C.c_int, [C.c_void_p, C.c_void_p]),
+            "clrrt_xchg_records": (C.c_void_p, [C.c_void_p]),
+            "clrrt_xchg_stats": (C.c_int, [C.c_void_p, P(C.c_int64)]),
+            "clrrt_xchg_destroy": (None, [C.c_void_p]),
+            "clrrt_xchg_selftest_concat": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, P(C.c_int32), P(C.c_double),
+                                                     P(C.c_int64), P(C.c_double), C.c_int32, C.c_void_p, C.c_int64,
+                                                     P(C.c_int64)]),
+        }
+        for name, (res, args) in sigs.items():
+            fn = getattr(L, name)
+            fn.restype = res
+            fn.argtypes = args
+        _xlib = L
+    return _xlib
+
+
+UID_BYTES = 128  # CLRRT_XCHG_UID_BYTES
+
+
+class NativeExchange:
+    """ShardExchange's job without Python in the rounds: the hook is libclrrt_xchg's C function (clrrt_xchg_hook,
+    include/clrrt_xchg.h) over its RCCL transport -- ncclAllGather on the engine's stream, k_xchg_concat, one read
+    of the pinned summary -- so clrrt_expand calls no Python (and takes no GIL) per round.  One process per GPU; the
+    process group only carries the communicator's unique id from its rank 0 to the others, once.  With a world of 1
+    the planner keeps the hook only under its option "shard_hook_world1" (set it before constructing this)."""
+
+    def __init__(self, planner, cap_records, device, group=None, first_bound=None, slice_size=None):
+        import ctypes as C
+        from . import ClrrtError
+        L = xchg_lib()
+        self.L = L
+        self.world = dist.get_world_size(group)
+        self.rank = dist.get_rank(group)
+        if first_bound is None:
+            first_bound = int(slice_size) + 64 if slice_size else 1024  # as ShardExchange
+        dev = torch.device(device)
+        index = dev.index if dev.index is not None else torch.cuda.current_device()
+        uid = (C.c_ubyte * UID_BYTES)()
+        if self.rank == 0 and L.clrrt_xchg_unique_id(uid) != 0:
+            raise ClrrtError(f"clrrt_xchg_unique_id: {L.clrrt_xchg_last_error().decode()}")
+        box = [bytes(uid)]
+        if self.world > 1:
+            dist.broadcast_object_list(box, src=dist.get_global_rank(group, 0) if group is not None else 0, group=group)
+        uid = (C.c_ubyte * UID_BYTES).from_buffer_copy(box[0])
+        h = C.c_void_p()
+        if L.clrrt_xchg_create_rccl(uid, self.rank, self.world, index, int(cap_records), int(first_bound),
+                                    C.byref(h)) != 0:
+            raise ClrrtError(f"clrrt_xchg_create_rccl: {L.clrrt_xchg_last_error().decode()}")
+        self.h = h
+        self.cap = int(cap_records)
+        if L.clrrt_xchg_attach(h, planner.h) != 0:
+            msg = L.clrrt_xchg_last_error().decode()
+            self.close()
+            raise ClrrtError(f"clrrt_xchg_attach: {msg}")
+        self._planner = planner
+
+    def records_ptr(self):
+        return self.L.clrrt_xchg_records(self.h)
+
+    def stats(self):
+        """exchanges, collectives, second gathers, closing exchanges, rows sent, rows received, the row bound."""
+        import ctypes as C
+        out = (C.c_int64 * 8)()
+        self.L.clrrt_xchg_stats(self.h, out)
+        keys = ("exchanges", "collectives", "second_gathers", "closing", "rows_sent", "rows_received", "bound")
+        return dict(zip(keys, (int(v) for v in out)))
+
+    rounds = property(lambda self: self.stats()["exchanges"])
+    collectives = property(lambda self: self.stats()["collectives"])
+    second_gathers = property(lambda self: self.stats()["second_gathers"])
+    closing = property(lambda self: self.stats()["closing"])
+
+    def close(self):
+        """Detach from the planner (sharding off) and free the communicator and the buffers."""
+        if getattr(self, "h", None):
+            pl = getattr(self, "_planner", None)
+            if pl is not None and pl.h:
+                pl.set_shards(0, 1)
+            self.L.clrrt_xchg_destroy(self.h)
+            self.h = None
+
+
 def exchange_capacity(max_batch, defer_steps=0, sim_dt=0.04):
     """Records one rank may commit in a round: 2 per sample of its slice and of its deferred samples (at
     most the ring's R - 1 earlier rounds: R = ceil(2 n_steps / T) + 2, clrrt_capi.hip ensure_defer)."""

@@ -347,6 +347,9 @@ struct clrrt_ctx {
     // with -- so every rank leaves the expansion instead of waiting in a collective the failed rank never joins
     bool poison_seen = false;      // an exchange of this expansion reported another rank's failure
     bool fn_failed = false;        // the exchange hook itself failed (the collective is broken: no more calls)
+    // option "shard_hook_world1": clrrt_set_shards with world 1 keeps dev_local and the hook, and the expansion
+    // runs the sharded commit path with one rank (a set hook, not world > 1, is what selects that path)
+    bool hook_world1 = false;
   } sh;
   // option "fail_at_round" k (fault injection, tests): the k-th commit from now fails with CLRRT_ECAPACITY
   // after the round's deferred-sample bookkeeping, as the "trajectory arena full" check does
@@ -1467,6 +1470,7 @@ int clrrt_set_option(clrrt_ctx* c, const char* key, int64_t value) {
   else if (k == "nn_debug" && value >= 0) c->nn_debug = (int)value;  // diagnostics: changes results
   else if (k == "fail_at_round" && value >= 0 && value < INT_MAX) c->fail_at_round = (int)value;  // fault injection
   else if (k == "fail_after_exchange" && value >= 0 && value < INT_MAX) c->fail_after_exchange = (int)value;
+  else if (k == "shard_hook_world1") c->sh.hook_world1 = value != 0;  // read by the next clrrt_set_shards
   else if (k == "roll_blocks" && value >= 0 && value < (1 << 20)) c->roll_blocks = (int)value;
   else if (k == "nn_pipeline") c->nn_pipeline = value != 0;
   else if (k == "roll_priority") c->roll_priority = value != 0;
@@ -2223,7 +2227,7 @@ static int compact_and_copy(clrrt_ctx* c, int L, int* n_out, bool merge_bbox) {
   const int V = defer ? d.nd_eval + L : L;
   {
     KTimer kt(c, 2);
-    const bool tag = defer && c->sh.world > 1;  // the exchange orders deferred samples by age
+    const bool tag = defer && c->sh.fn;  // the exchange orders deferred samples by age
     HIPC(c, launch_compact(st, V, c->d_samples, c->cand, c->regnodes, c->gbnodes, c->so, c->n_rows, c->rank,
                            c->out_nodes, c->jobs, c->totals, c->cmp, tag ? d.slot : 0, tag ? d.R : 0,
                            (int)c->cap.max_batch, c->totals_zeroed));
@@ -2309,7 +2313,7 @@ static int ensure_defer(clrrt_ctx* c) {
   const int n = std::max(1, c->dp.n_steps_max);
   const int R = (int)((2LL * n + d.T - 1) / d.T) + 2;
   // sharded rounds carry a record's origin-round age in 8 bits (k_compact_scatter / k_xorder_keys)
-  if (c->sh.world > 1 && R > 256)
+  if (c->sh.fn && R > 256)
     return fail(c, CLRRT_EINVAL, "defer_steps too small for sharded rounds (more than 256 rounds in flight)");
   if (!d.res || d.R < R) {
     HIPC(c, hipStreamSynchronize(c->stream));
@@ -2463,7 +2467,7 @@ static int flush_replays(clrrt_ctx* c) {
 static int defer_drain(clrrt_ctx* c, int64_t* goal_nodes) {
   auto& d = c->def;
   if (!d.active) return CLRRT_OK;
-  const bool sharded = c->sh.world > 1;  // every rank takes part in the drain's exchange
+  const bool sharded = c->sh.fn != nullptr;  // every rank takes part in the drain's exchange
   if (d.nd > 0 || d.ncarry > 0 || sharded) {
     hipStream_t st = c->stream;
     {
@@ -2765,7 +2769,7 @@ static inline void shard_slice(const clrrt_ctx* c, int64_t g, int64_t* f, int* n
 // left at the same exchange (an error flag seen there) or the collective itself failed.  Returns the final status.
 static int shard_expansion_end(clrrt_ctx* c, int rc) {
   auto& h = c->sh;
-  if (h.world > 1 && !h.poison_seen && !h.fn_failed) {
+  if (h.fn && !h.poison_seen && !h.fn_failed) {
     clrrt_exchange_io io;
     memset(&io, 0, sizeof(io));
     io.flags = 1;
@@ -2800,7 +2804,7 @@ static void shard_expansion_begin(clrrt_ctx* c) {
 static int commit_round(clrrt_ctx* c, int nn, double elapsed_ms, int* n_app) {
   auto& h = c->sh;
   *n_app = 0;
-  if (h.world <= 1) {
+  if (!h.fn) {
     *n_app = nn;
     const int rc = append_nodes(c, c->out_nodes, nn);
     if (rc == CLRRT_OK) c->round_sizes.push_back(c->n_nodes);
@@ -3007,7 +3011,7 @@ static int expand_lag2(clrrt_ctx* c, clrrt_rng* rng, int64_t n_iters, double bud
   clrrt_rng work = *rng, committed = *rng;
   std::deque<clrrt_sample> pending;
   const int cur = batch;  // samples per round, all ranks
-  const bool sharded = c->sh.world > 1;
+  const bool sharded = c->sh.fn != nullptr;
   c->sh.max_ms = 0;
   c->sh.nd_global = 0;
   c->sh.rows_stop = 0;
@@ -3311,7 +3315,7 @@ int clrrt_expand(clrrt_ctx* c, clrrt_rng* rng, int64_t n_iters, double budget_ms
   if (n_iters == 0 && !(budget_ms > 0)) return CLRRT_EINVAL;
   if (c->n_nodes <= 0) return fail(c, CLRRT_ESTATE, "tree not initialised");
   c->round_sizes.clear();
-  const bool sharded = c->sh.world > 1;
+  const bool sharded = c->sh.fn != nullptr;
   if (sharded && mode != CLRRT_MODE_BATCH) return fail(c, CLRRT_EINVAL, "sharded expansion runs BATCH rounds only");
   HIPC(c, hipSetDevice(c->device));
   // samples per round (all ranks when sharded: each rank's slice must fit max_batch)
@@ -3456,17 +3460,19 @@ int clrrt_expand(clrrt_ctx* c, clrrt_rng* rng, int64_t n_iters, double budget_ms
 int clrrt_set_shards(clrrt_ctx* c, int32_t rank, int32_t world, void* dev_local, int32_t cap_local,
                      clrrt_exchange_fn exchange, void* user) {
   if (!c || world < 1 || rank < 0 || rank >= world) return CLRRT_EINVAL;
-  if (world > 1 && (!dev_local || cap_local <= 0 || !exchange)) return CLRRT_EINVAL;
+  // one rank keeps the hook only with option "shard_hook_world1" (and a hook to keep)
+  const bool on = world > 1 || (c->sh.hook_world1 && exchange != nullptr);
+  if (on && (!dev_local || cap_local <= 0 || !exchange)) return CLRRT_EINVAL;
   HIPC(c, hipSetDevice(c->device));
   auto& h = c->sh;
   h.rank = rank;
   h.world = world;
-  h.dev_local = world > 1 ? dev_local : nullptr;
-  h.cap_local = world > 1 ? cap_local : 0;
-  h.fn = world > 1 ? exchange : nullptr;
-  h.user = world > 1 ? user : nullptr;
+  h.dev_local = on ? dev_local : nullptr;
+  h.cap_local = on ? cap_local : 0;
+  h.fn = on ? exchange : nullptr;
+  h.user = on ? user : nullptr;
   c->rank = rank;  // owner of this rank's records
-  if (world > 1 && !h.d_goal) HIPC(c, dalloc(&h.d_goal, 1));
+  if (on && !h.d_goal) HIPC(c, dalloc(&h.d_goal, 1));
   return CLRRT_OK;
 }
 

@@ -315,7 +315,9 @@ int clrrt_expand(clrrt_ctx* ctx, clrrt_rng* rng, int64_t n_iters, double budget_
  * ranks that failed) and in io->bbox_all the union of the ranks' `bbox_local` (the walk index's frame).  Every
  * rank then appends the same records in the same order (deferred samples: the oldest round first), so the trees
  * stay identical.  The caller chooses weak scaling (batch = world x per-GPU samples) or strong scaling (batch
- * fixed).  world = 1 turns sharding off.  dev_local holds cap_local records (>= 2 x the slice, + the deferred
+ * fixed).  world = 1 turns sharding off -- unless the option "shard_hook_world1" is 1 (default 0), with which a
+ * clrrt_set_shards(world = 1) keeps dev_local and the hook and the expansion runs the sharded commit path with its
+ * one rank (include/clrrt_xchg.h's one-rank communicator; results are those of world = 1 without it).  dev_local holds cap_local records (>= 2 x the slice, + the deferred
  * samples).
  * No host synchronisation (ABI 11): the engine writes dev_local on io->stream and calls the hook without waiting
  * for it, so the hook's collective must be ordered after io->stream's work (a stream wait on an event, or the

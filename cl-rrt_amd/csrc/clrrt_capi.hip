@@ -119,7 +119,10 @@ struct clrrt_ctx {
   // -> cfg3 1.289 / 1.293 / 1.274 / 1.232 M nodes/s, profiles/r06k_*)
   int nnw_hscale = 50;
   int nnw_lpt = 0;          // option "nn_walk_lpt": optimize samples first in each XCD's eighth (k_walk_lpt)
-  int nnw_index = 5;        // option "nn_walk_index": the index's place order (WalkBufs::index_kind); 5 since round 6
+  int nnw_root_seed = 1;    // option "nn_root_seed": optimize samples start from the root roster (WalkBufs::roster)
+  int nnw_root_k = 64;      // option "nn_root_k": roster entries
+  int nnw_root_scan = 16384;  // option "nn_root_scan": ids scanned for them
+  int nnw_index = 5;       // option "nn_walk_index": the index's place order (WalkBufs::index_kind); 5 since round 6
   int nnw_lds_floor = 0;    // option "nn_walk_lds_floor": LDS bytes each walk wave reserves at least
   // option "nn_walk_waves": the walk's persistent grid (waves taking samples from per-XCD counters; 0 = one
   // wave per sample; -1, the default: 9 per CU).  A fixed grid leaves wave slots to the kernels that run
@@ -1449,6 +1452,13 @@ int clrrt_set_option(clrrt_ctx* c, const char* key, int64_t value) {
     c->nnw.sorted_n = c->nnw_alt.sorted_n = c->nnw3.sorted_n = -1;
   }
   else if (k == "nn_walk_lpt") c->nnw_lpt = value != 0;  // scheduling only: same lists
+  else if (k == "nn_root_seed" || (k == "nn_root_k" && value >= 1 && value <= 64) ||
+           (k == "nn_root_scan" && value >= 1 && value <= 32768)) {  // same lists; a kept index has the old marks
+    if (k == "nn_root_seed") c->nnw_root_seed = value != 0;
+    else if (k == "nn_root_k") c->nnw_root_k = (int)value;
+    else c->nnw_root_scan = (int)value;
+    c->nnw_built.n = -1;
+  }
   else if (k == "nn_walk_index" && value >= 0 && value <= 5) {
     c->nnw_index = (int)value;
     c->nnw_built.n = -1;  // the kept index and sort results have the old order
@@ -1605,7 +1615,8 @@ static int alloc_walk(clrrt_ctx* c, WalkBufs& w) {
   HIPC(c, dalloc(&w.supers, walk_super_count(c->cap.max_nodes) + 1));
   HIPC(c, dalloc(&w.ovf_n, 1));
   HIPC(c, dalloc(&w.ovf, kWalkMaxOver));
-  HIPC(c, dalloc(&w.wctr, 8));
+  HIPC(c, dalloc(&w.wctr, 8 + 2 + 64));  // + the root roster (count, X, 64 ids), freed with it
+  w.roster = w.wctr + 8;
   HIPC(c, dalloc(&w.pk, (int64_t)kWalkMaxOver * kWalkMaxChunks * 11));
   HIPC(c, dalloc(&w.pi, (int64_t)kWalkMaxOver * kWalkMaxChunks * 11));
   HIPC(c, dalloc(&w.skeys, Mp));
@@ -1632,6 +1643,9 @@ static int ensure_walk_set(clrrt_ctx* c, WalkBufs& w) {
   w.index_kind = c->nnw_index;
   w.hscale_pct = c->nnw_hscale;
   w.lpt = c->nnw_lpt;
+  w.root_seed = c->nnw_root_seed;
+  w.root_k = c->nnw_root_k;
+  w.root_scan = c->nnw_root_scan;
   w.lds_floor = c->nnw_lds_floor;
   w.waves = c->nnw_waves < 0 ? 9 * c->n_cu : c->nnw_waves;
   // the default grid serves batches of >= 4x its waves (cfg2's 4096-sample rounds run 4% faster with one

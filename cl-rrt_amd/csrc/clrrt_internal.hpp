@@ -192,7 +192,8 @@ struct WalkBufs {
   float4 *P, *Q;           // [max_nodes + 1024] (x, y, c, s), (bx, by, ca, sa) relative to the frame origin
   float* CE;               // costE
   int* ID;                 // node id (-1: padding)
-  int* HEAD;               // first record of the run of records with equal Dubins-key inputs
+  int* HEAD;               // first record of the run of records with equal Dubins-key inputs (| WALK_ROOT_BIT: the
+                           // run's key inputs are node 0's, whichever sector run it is)
   int2* trun;              // per tile: (run head, smallest id) of a tile inside one run, else (-1, -1)
   WalkTile *tiles, *supers;
   // overflow of the walk: a sample whose walk passes the budget (tiles visited / exact keys) hands
@@ -214,6 +215,13 @@ struct WalkBufs {
   int index_kind = 0;
   int hscale_pct = 100;  // the 3D codes' heading axis: percent of rho metres per radian (option nn_walk_hscale)
   int* wctr = nullptr;  // [8] the per-XCD sample counters
+  // the root roster (option nn_root_seed; clrrt_nnwalk.hip header): [0] entries n <= root_k, [1] X (every node of
+  // id <= X whose key inputs equal node 0's is listed), [2 .. 2 + n) their ids, ascending.  Written by every
+  // launch_nn_walk_build of the set (empty for a range index); null: the set's searches take no seed.
+  int* roster = nullptr;
+  int root_seed = 1;       // 0: no roster, no root-class marks in HEAD (the walk as it was)
+  int root_k = 64;         // roster entries (<= 64: one per lane)
+  int root_scan = 16384;   // ids [0, min(N, root_scan)) are scanned for them (<= 32768)
   int lpt = 0;          // the persistent grid's eighths: optimize samples first (k_walk_lpt, option nn_walk_lpt)
   // set by the caller around one launch_nn_walk_search: [B] key caps for the appended-node search written right after
   // the main grid (k_walk_seed), and an event recorded there (before the overflow split); null: neither

@@ -35,6 +35,24 @@
 //     |sample - ref.back()| >= 2.1 ref_res.
 // A skipped node, tile or super-tile can hold no pair that enters the list, so every list equals
 // the brute-force one bit for bit (ties included: pairs are ordered by (key, node index) in both).
+//
+// Root seed (option nn_root_seed; optimize samples of the main walk, not its overflow split nor the appended-node
+// walk).  The copies of the root pose -- the root and its zero-length children: node 0's x, y, rotation and costE --
+// share one optimize key per sample, kr = costE + dubins(root -> sample), and tie in node id order, so on grown trees
+// most optimize lists are the first 11 feasible copies by id (tools/root_seed_depth.py).  The index places the copies
+// by ref.back() in 8 sector runs, where the walk met the small ids late.  So every whole-tree build also makes the
+// root roster (k_wscan_top): the first K = 64 ids among [0, min(N, S)), S = 16384, whose key inputs equal node 0's
+// (k_walk_gather's ==), in ascending id, and X = the K-th of them (min(N, S) - 1 when there are fewer): every member
+// with id <= X is listed.  The class's records carry WALK_ROOT_BIT in HEAD (and trun), whichever run they lie in.
+// walk_one computes kr from node 0 as drain_exact forms a key, runs feasible_search on the roster (one entry per
+// lane), starts the list from the first 11 feasible (kr, id) pairs and then rejects a root-class record when
+// id <= X or (kr, id) does not precede the 11th entry, and a root-class tile by its smallest id under the latter.
+// It is exact: members share node 0's key inputs bit for bit, hence kr; each seeded pair is a feasible pair by the
+// search's own decider; the roster is complete up to X, so a member at or below X is either seeded, infeasible, or
+// follows 11 seeded pairs; members above X are cut only where (kr, id) does not precede the current 11th pair, a
+// bound that only tightens.  The roster is rebuilt with every index (no state outlives it); range indexes
+// (first > 0) and the appended-node index get none.  An overflow record still hands over (11th key, id + 1) only:
+// its split waves re-find the pairs.
 #include <hip/hip_runtime.h>
 #include <climits>
 #include <hip/hip_fp16.h>
@@ -75,7 +93,11 @@ namespace clrrt {
 #define WALK_SECTOR_BITS 3  // 2^WALK_SECTOR_BITS >= WALK_APBINS
 #endif
 
-#define LAUNCH_CHECK3()                          \
+#define WALK_ROOT_BIT 0x40000000  // in HEAD / trun.x: the run's key inputs equal node 0's (place indices stay below it)
+#define WALK_ROOT_KMAX 64         // roster entries: one per lane of the seeding wave
+#define WALK_ROOT_SMAX 32768      // ids scanned for them at most (k_wscan_top: 32 per thread)
+
+#define LAUNCH_CHECK3()                        \
   do {                                           \
     hipError_t e_ = hipGetLastError();           \
     if (e_ != hipSuccess) return e_;             \
@@ -251,7 +273,7 @@ __global__ void k_walk_trun(const int* __restrict__ HEAD, const int* __restrict_
 // Place-ordered float records (relative to the frame origin); entries N .. Npad are padding (id -1).
 __global__ void k_walk_gather(const NnRec* __restrict__ nodes, int N, int Npad, const int* __restrict__ order,
                               double ox, double oy, float4* __restrict__ P, float4* __restrict__ Q,
-                              float* __restrict__ CE, int* __restrict__ ID, int* __restrict__ dup) {
+                              float* __restrict__ CE, int* __restrict__ ID, int* __restrict__ dup, int mark_root) {
   const int j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= Npad) return;
   if (j < N) {
@@ -267,9 +289,16 @@ __global__ void k_walk_gather(const NnRec* __restrict__ nodes, int N, int Npad, 
       const NnRec& o = nodes[order[j - 1]];
       same = r.x == o.x && r.y == o.y && r.c == o.c && r.s == o.s && r.costE == o.costE;
     }
-    dup[j] = same ? -1 : j;
+    // run markers 2 j + (the run is of the root class: the same comparison with node 0); the max-scan carries
+    // a head's marker over its run and k_wscan_fix turns it into HEAD's (place index | WALK_ROOT_BIT)
+    bool root = false;
+    if (mark_root) {
+      const NnRec& o = nodes[0];
+      root = r.x == o.x && r.y == o.y && r.c == o.c && r.s == o.s && r.costE == o.costE;
+    }
+    dup[j] = same ? -1 : 2 * j + (root ? 1 : 0);
   } else {
-    dup[j] = j;
+    dup[j] = 2 * j;
     P[j] = make_float4(0.f, 0.f, 1.f, 0.f);
     Q[j] = make_float4(0.f, 0.f, 1.f, 0.f);
     CE[j] = 0.f;
@@ -677,6 +706,42 @@ __device__ __forceinline__ int lc_le(float v) {  // the largest code c with lc_d
 // SHARE = false (the appended-node search, k_walk_delta): SPLIT's start from (kb, ib) -- there the sample's key cap,
 // (cap, INT_MAX): every pair with key <= cap is kept -- over all super-tiles (nch 1), without the records' shared
 // word; the list goes to pk / pi row o_sp.
+// Root seed of one optimize sample (header comment): the class's key from node 0, formed as drain_exact forms a key,
+// feasible_search on the roster's entries, one per lane, and the first NN_K feasible (kr, id) pairs -- lanes are in
+// id order and the keys equal, so entry q is the q-th feasible one -- into the empty list (lk, li).  Returns the
+// entries seeded, or -1 without a seed (empty roster, or a NaN key, which enters no list).
+#ifndef WALK_SEED_INLINE
+#define WALK_SEED_INLINE __forceinline__
+#endif
+__device__ WALK_SEED_INLINE int walk_root_seed(double sx, double sy, const NnRec* __restrict__ nodes,
+                                               const int* __restrict__ roster, double feas_len, int lane, float& kr,
+                                               int& rX, float& lk, int& li) {
+  const int rn = uni(roster[0]);
+  if (rn <= 0) return -1;
+  const NnRec& r0 = nodes[0];
+  float k0 = dubins_key(sx, sy, r0.x, r0.y, r0.c, r0.s);
+  k0 = uni(r0.costE + k0);
+  if (!(k0 == k0)) return -1;
+  kr = k0;
+  rX = uni(roster[1]);
+  bool c = false;
+  int id = 0x7fffffff;
+  if (lane < rn) {
+    id = roster[2 + lane];
+    const NnRec& r = nodes[id];
+    c = feasible_search(sx, sy, r.bx, r.by, r.ca, r.sa, r.ang_par, feas_len);
+  }
+  uint64_t m = __ballot(c);
+  int q = 0;
+  for (; m && q < NN_K; q++) {
+    const int l = __ffsll((unsigned long long)m) - 1;
+    m &= m - 1;
+    const int i = __shfl(id, l, 64);
+    if (lane == q) { lk = k0; li = i; }
+  }
+  return q;
+}
+
 template <int FMT, bool SPLIT, bool BRK, bool SHARE = SPLIT>
 __device__ __forceinline__ void walk_one(const clrrt_sample* __restrict__ S, int B,
                                                     const NnRec* __restrict__ nodes, const float4* __restrict__ P,
@@ -691,7 +756,8 @@ __device__ __forceinline__ void walk_one(const clrrt_sample* __restrict__ S, int
                                                     unsigned long long* __restrict__ stats, int bud_tiles,
                                                     int bud_ex, int* __restrict__ ovf_n, int4* __restrict__ ovf,
                                                     int max_over, int nch, float* __restrict__ pk,
-                                                    int* __restrict__ pi, int nloc_max, int s, int ch, int nloc, float kb, int ib, int o_sp) {
+                                                    int* __restrict__ pi, int nloc_max, int s, int ch, int nloc, float kb, int ib, int o_sp,
+                                                    const int* __restrict__ roster = nullptr) {
   // LDS is indexed by the wave's local super-tile index l (super-tile gst(l))
   constexpr bool STATE = FMT == WALK_FMT_STATE, CODED = FMT == WALK_FMT_CODED;
   extern __shared__ uint8_t s_lb[];  // [nloc] bounds of the super-tiles' remaining tiles (stateless) ...
@@ -745,6 +811,24 @@ __device__ __forceinline__ void walk_one(const clrrt_sample* __restrict__ S, int
 #endif
   int hc = -1;       // run head whose key is known ...
   float kc = 0.f;    // ... and that key
+  // root seed (optimize samples of the main walk).  Its state lives in LDS, not in registers the whole walk would
+  // carry (the walk kernels spill as they are; a root-class record is the rare case for most samples): s_root[0] =
+  // the root class's key kr (-inf: not seeded, so the class rule never fires), [1] = the roster's reach rX (members
+  // with id <= rX are accounted for), [2] = -1 not seeded, else the entries seeded, + 256 once a pair has been
+  // inserted since
+  __shared__ int s_root[4];
+  int seeded = -1;
+  if constexpr (!SPLIT) {
+    float kr = -__builtin_inff();
+    int rX = -1;
+    if (roster && !ex) seeded = walk_root_seed(sx, sy, nodes, roster, p.feas_len, lane, kr, rX, lk, li);
+    if (lane == 0) {
+      s_root[0] = __float_as_int(kr);
+      s_root[1] = rX;
+      s_root[2] = seeded;
+    }
+    __builtin_amdgcn_wave_barrier();
+  }
   unsigned long long n_sup = 0, n_tile = 0, n_q = 0, n_ex = 0, n_und = 0, n_sure = 0, n_drop = 0;
 
   auto refresh = [&]() __attribute__((always_inline)) {
@@ -816,7 +900,7 @@ __device__ __forceinline__ void walk_one(const clrrt_sample* __restrict__ S, int
     // e.g. the root's zero-length children, are the ones whose remaining records this saves)
     {
       const int hd = lane < nq ? HEAD[j] : 0;
-      const int depth = lane < nq ? j - hd : -1;
+      const int depth = lane < nq ? j - (hd & ~WALK_ROOT_BIT) : -1;  // (hc keeps the class bit, as HEAD and trun do)
       int best = depth;
 #pragma unroll
       for (int o = 32; o > 0; o >>= 1) best = max(best, __shfl_xor(best, o, 64));
@@ -848,6 +932,9 @@ __device__ __forceinline__ void walk_one(const clrrt_sample* __restrict__ S, int
       if (w_less(k, i, kth, idk)) {
         w_insert(lk, li, k, i, lane);
         refresh();
+        if constexpr (!SPLIT) {
+          if (lane == 0) s_root[2] |= 256;
+        }
       }
     }
     n2 = 0;
@@ -915,6 +1002,12 @@ __device__ __forceinline__ void walk_one(const clrrt_sample* __restrict__ S, int
   // Necessary conditions for record j to enter the list (the brute-force prefilter + turning bound).
   auto prefilter = [&](int id, int hd, float4 pp, float4 qq, float ce) __attribute__((always_inline)) -> bool {
     if (hd == hc && !w_less(kc, id, kth, idk)) return false;  // key known: kc
+    if constexpr (!SPLIT) {
+      // seeded: a root-class record's key is kr in whichever run; the roster has settled the ids up to rX
+      if (hd & WALK_ROOT_BIT) {
+        if (id <= s_root[1] || !w_less(__int_as_float(s_root[0]), id, kth, idk)) return false;
+      }
+    }
     const float qx = rsx - pp.x, qy = rsy - pp.y;
     const float d2 = qx * qx + qy * qy;
     float l2 = lim;
@@ -1022,6 +1115,9 @@ __device__ __forceinline__ void walk_one(const clrrt_sample* __restrict__ S, int
   // identical records on large trees; optimize samples' lists fill with their smallest ids.)
   auto run_out = [&](int tl) -> bool {
     const int2 tr = trun[tl];
+    if constexpr (!SPLIT) {  // seeded: a root-class tile by kr, whichever run it lies in
+      if (tr.x >= 0 && (tr.x & WALK_ROOT_BIT) && !w_less(__int_as_float(s_root[0]), tr.y, kth, idk)) return true;
+    }
     return tr.x >= 0 && tr.x == hc && !w_less(kc, tr.y, kth, idk);
   };
   // Tile stack (LDS, WALK_TQ entries: tile, bound), wave-uniform depth.  Tiles the list has pruned since
@@ -1158,6 +1254,9 @@ __device__ __forceinline__ void walk_one(const clrrt_sample* __restrict__ S, int
     }
   };
   if (SPLIT) refresh();  // the initial bound
+  if constexpr (!SPLIT) {
+    if (seeded >= 0) refresh();  // the seeded list's bound
+  }
   float mlb = __builtin_inff();
   for (int t0 = 0; t0 < nloc; t0 += 64) {
     const int t = t0 + lane;
@@ -1258,6 +1357,11 @@ __device__ __forceinline__ void walk_one(const clrrt_sample* __restrict__ S, int
     }
   } else {
     walk_emit(lk, li, lane, s, p.sort_limit, cand, ckey, ncand, ctie);
+    if (stats && lane == 0) {  // (work_ctr[27] / [63]: samples that finish here, not the overflow's)
+      const int seed_st = s_root[2];
+      if (seed_st > 0 && seed_st < 256) atomicAdd(&stats[9], 1ull);              // the final list is the seeded list
+      if (seed_st >= 0 && (seed_st & 255) < NN_K) atomicAdd(&stats[45], 1ull);  // seeded with fewer than NN_K entries
+    }
   }
   flush_stats();
 }
@@ -1279,7 +1383,8 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CLRRT_W
                                                     unsigned long long* __restrict__ stats, int bud_tiles,
                                                     int bud_ex, int* __restrict__ ovf_n, int4* __restrict__ ovf,
                                                     int max_over, int nch, float* __restrict__ pk,
-                                                    int* __restrict__ pi, int nloc_max, int* __restrict__ wctr) {
+                                                    int* __restrict__ pi, int nloc_max, int* __restrict__ wctr,
+                                                    const int* __restrict__ roster) {
   if constexpr (SPLIT) {
     const int o = (int)blockIdx.x / nch;
     const int ch = (int)blockIdx.x % nch;
@@ -1298,7 +1403,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CLRRT_W
       if (t >= B) return;
       walk_one<FMT, SPLIT, BRK>(S, B, nodes, P, Q, CE, ID, HEAD, trun, tiles, ntiles, sup, nsup, p, fr, cand, ckey, ncand,
                                 ctie, sorder, stats, bud_tiles, bud_ex, ovf_n, ovf, max_over, nch, pk, pi, nloc_max,
-                                sorder[t], 0, nsup, __builtin_inff(), 0x7fffffff, 0);
+                                sorder[t], 0, nsup, __builtin_inff(), 0x7fffffff, 0, roster);
       return;
     }
     int k = 0;
@@ -1313,7 +1418,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CLRRT_W
         k++;
       }
       if (t < 0) break;
-      walk_one<FMT, SPLIT, BRK>(S, B, nodes, P, Q, CE, ID, HEAD, trun, tiles, ntiles, sup, nsup, p, fr, cand, ckey, ncand, ctie, sorder, stats, bud_tiles, bud_ex, ovf_n, ovf, max_over, nch, pk, pi, nloc_max, sorder[t], 0, nsup, __builtin_inff(), 0x7fffffff, 0);
+      walk_one<FMT, SPLIT, BRK>(S, B, nodes, P, Q, CE, ID, HEAD, trun, tiles, ntiles, sup, nsup, p, fr, cand, ckey, ncand, ctie, sorder, stats, bud_tiles, bud_ex, ovf_n, ovf, max_over, nch, pk, pi, nloc_max, sorder[t], 0, nsup, __builtin_inff(), 0x7fffffff, 0, roster);
       __builtin_amdgcn_wave_barrier();
     }
   }
@@ -1487,7 +1592,8 @@ __global__ void __launch_bounds__(64) k_walk_audit(const clrrt_sample* __restric
       n_head += __popcll(__ballot(head));
       n_s1 += __popcll(__ballot(s1));
       n_rec += __popcll(__ballot(idj >= 0));
-      const bool inrun = idj >= 0 && (HEAD[j] != j || (j + 1 < Npad && HEAD[j + 1] == j));
+      const bool inrun = idj >= 0 && ((HEAD[j] & ~WALK_ROOT_BIT) != j ||
+                                      (j + 1 < Npad && (HEAD[j + 1] & ~WALK_ROOT_BIT) == j));
       n_inrun += __popcll(__ballot(inrun));
     }
   }
@@ -1576,9 +1682,53 @@ __global__ void __launch_bounds__(256) k_wscan_tiles(const int* __restrict__ in,
   if (threadIdx.x == 255) tmax[blockIdx.x] = max(x, pre);
 }
 
-__global__ void __launch_bounds__(1024) k_wscan_top(int* __restrict__ tmax, int nt) {
+// (the build's one-block launch; it also makes the root roster: roster != null, nscan = min(N, S) ids to scan, 0 for an
+// empty roster (range indexes, option off).  The ids' class flags are read coalesced into an LDS bitmap, thread t
+// then owns ids [t per, (t + 1) per), a block sum-scan ranks the members, and the first K are written in id order.)
+__global__ void __launch_bounds__(1024) k_wscan_top(int* __restrict__ tmax, int nt, const NnRec* __restrict__ nodes,
+                                                    int nscan, int K, int* __restrict__ roster) {
   // exclusive max-scan of the tile maxima, one block (sequential chunks per thread)
   __shared__ int s_t[1024];
+  __shared__ unsigned long long s_bits[WALK_ROOT_SMAX / 64];
+  if (roster) {
+    const NnRec& o = nodes[0];
+    for (int i0 = 0; i0 < nscan; i0 += 1024) {
+      const int i = i0 + (int)threadIdx.x;
+      bool m = false;
+      if (i < nscan) {
+        const NnRec& r = nodes[i];
+        m = r.x == o.x && r.y == o.y && r.c == o.c && r.s == o.s && r.costE == o.costE;
+      }
+      const unsigned long long b = __ballot(m);
+      if ((threadIdx.x & 63) == 0) s_bits[i >> 6] = b;
+    }
+    __syncthreads();
+    const int rper = (nscan + 1023) / 1024;  // <= 32
+    const int rb = min(nscan, (int)threadIdx.x * rper), re = min(nscan, rb + rper);
+    uint32_t mine = 0;
+    for (int i = rb; i < re; i++) mine |= (uint32_t)((s_bits[i >> 6] >> (i & 63)) & 1ull) << (i - rb);
+    const int cnt = __popc(mine);
+    s_t[threadIdx.x] = cnt;
+    __syncthreads();
+    for (int o2 = 1; o2 < 1024; o2 <<= 1) {  // inclusive sum-scan of the threads' member counts
+      const int y = threadIdx.x >= o2 ? s_t[threadIdx.x - o2] : 0;
+      __syncthreads();
+      s_t[threadIdx.x] += y;
+      __syncthreads();
+    }
+    const int total = s_t[1023];
+    int pos = s_t[threadIdx.x] - cnt;
+    for (uint32_t mm = mine; mm && pos < K; mm &= mm - 1, pos++) {
+      const int i = rb + __ffs(mm) - 1;
+      roster[2 + pos] = i;
+      if (pos == K - 1) roster[1] = i;  // X: the K-th member's id
+    }
+    if (threadIdx.x == 0) {
+      roster[0] = min(total, K);
+      if (total < K) roster[1] = nscan - 1;  // the whole scanned range is covered (-1: nothing is)
+    }
+    __syncthreads();
+  }
   const int per = (nt + 1023) / 1024;
   const int b = threadIdx.x * per, e = min(nt, b + per);
   int m = INT_MIN;
@@ -1600,12 +1750,16 @@ __global__ void __launch_bounds__(1024) k_wscan_top(int* __restrict__ tmax, int 
 }
 
 __global__ void __launch_bounds__(256) k_wscan_fix(int* __restrict__ out, int n, const int* __restrict__ tpre) {
+  // (and the markers' decoding, k_walk_gather: 2 head + root flag -> head | WALK_ROOT_BIT; every marker is >= 0, the
+  // first record's being 0 or 1)
   const int t = blockIdx.x;
-  if (t == 0) return;
   const int p = tpre[t];
   for (int i = threadIdx.x; i < WSCAN_TILE; i += 256) {
     const int j = t * WSCAN_TILE + i;
-    if (j < n) out[j] = max(out[j], p);
+    if (j < n) {
+      const int v = max(out[j], p);
+      out[j] = (v >> 1) | ((v & 1) ? WALK_ROOT_BIT : 0);
+    }
   }
 }
 
@@ -1632,6 +1786,7 @@ hipError_t launch_nn_walk_build(hipStream_t st, const NnRec* nodes, int N, const
                                 double x1, double y1, WalkBufs& w, const WalkBufs* prev, int first) {
   if (N <= 0) return hipSuccess;
   if (first < 0 || N > w.cap_nodes) return hipErrorInvalidValue;  // the buffers' shapes (alloc_walk)
+  if (N > WALK_ROOT_BIT - WALK_TILE * WALK_SUPER) return hipErrorInvalidValue;  // place indices stay below the bit
   const int Npad = (N + WALK_TILE * WALK_SUPER - 1) / (WALK_TILE * WALK_SUPER) * (WALK_TILE * WALK_SUPER);
   const int ntiles = Npad / WALK_TILE, nsup = ntiles / WALK_SUPER;
   const int kind = w.index_kind;
@@ -1682,8 +1837,13 @@ hipError_t launch_nn_walk_build(hipStream_t st, const NnRec* nodes, int N, const
   w.sorted_scale = scale;
   w.sorted_kind = kind;
   // one-wave blocks (see launch_nn_delta)
+  // the root roster and the root-class marks: whole-tree indexes only (a range index gets an empty roster and no
+  // marks, so its searches run unseeded)
+  const bool rooted = first == 0 && w.root_seed != 0 && w.roster != nullptr;
+  const int rscan = rooted ? std::min(N, std::min(std::max(w.root_scan, 1), WALK_ROOT_SMAX)) : 0;
+  const int rk = std::min(std::max(w.root_k, 1), WALK_ROOT_KMAX);
   hipLaunchKernelGGL(k_walk_gather, dim3((Npad + 63) / 64), dim3(64), 0, st, nodes, N, Npad, w.sids, fr.ox, fr.oy,
-                     w.P, w.Q, w.CE, w.ID, w.vals);
+                     w.P, w.Q, w.CE, w.ID, w.vals, rooted ? 1 : 0);
   LAUNCH_CHECK3();
   // HEAD[j] = first record of j's run of equal key inputs (inclusive max-scan of dup markers)
   {
@@ -1691,7 +1851,7 @@ hipError_t launch_nn_walk_build(hipStream_t st, const NnRec* nodes, int N, const
     int* tmax = (int*)w.keys2;  // free between the two sorts
     hipLaunchKernelGGL(k_wscan_tiles, dim3(nt), dim3(256), 0, st, w.vals, Npad, w.HEAD, tmax);
     LAUNCH_CHECK3();
-    hipLaunchKernelGGL(k_wscan_top, dim3(1), dim3(1024), 0, st, tmax, nt);
+    hipLaunchKernelGGL(k_wscan_top, dim3(1), dim3(1024), 0, st, tmax, nt, nodes, rscan, rk, w.roster);
     LAUNCH_CHECK3();
     hipLaunchKernelGGL(k_wscan_fix, dim3(nt), dim3(256), 0, st, w.HEAD, Npad, tmax);
     LAUNCH_CHECK3();
@@ -1790,7 +1950,7 @@ hipError_t launch_nn_walk_search(hipStream_t st, const clrrt_sample* S, int B, c
 #define WALK_LAUNCH1(F, BK, PS)                                                                                  \
   hipLaunchKernelGGL((k_walk_search<F, false, BK, PS>), dim3(grid), dim3(64), lds, st, S, B, nodes, w.P,          \
                      w.Q, w.CE, w.ID, w.HEAD, w.trun, w.tiles, ntiles, w.supers, nsup, p, fr, cand, ckey, ncand, ctie,  \
-                     sorder, stats, bt, be, w.ovf_n, w.ovf, w.max_over, w.nch, w.pk, w.pi, nsup, wctr)
+                     sorder, stats, bt, be, w.ovf_n, w.ovf, w.max_over, w.nch, w.pk, w.pi, nsup, wctr, (const int*)w.roster)
 #define WALK_LAUNCH(F, BK)            \
   do {                                \
     if (pers) WALK_LAUNCH1(F, BK, true);  \
@@ -1827,7 +1987,7 @@ hipError_t launch_nn_walk_search(hipStream_t st, const clrrt_sample* S, int B, c
   hipLaunchKernelGGL((k_walk_search<WALK_FMT_STATE, true, BK>), dim3(w.max_over * w.nch), dim3(64),               \
                      2 * sizeof(float) * (size_t)nl, st, S, B, nodes, w.P, w.Q, w.CE, w.ID, w.HEAD, w.trun, w.tiles, \
                      ntiles, w.supers, nsup, p, fr, cand, ckey, ncand, ctie, sorder, stats, 0, 0, w.ovf_n, w.ovf,  \
-                     w.max_over, w.nch, w.pk, w.pi, nl, nullptr)
+                     w.max_over, w.nch, w.pk, w.pi, nl, nullptr, nullptr)
     if (brk) WALK_SPLIT(true);
     else WALK_SPLIT(false);
 #undef WALK_SPLIT

@@ -76,6 +76,10 @@ _SIGS = {
     "clrrt_selftest_math": (C.c_int, [C.c_void_p, C.c_int32, P(C.c_double), P(C.c_double), C.c_int32,
                                       P(C.c_double)]),
     "clrrt_selftest_units": (C.c_int, [C.c_void_p, C.c_int32, P(C.c_double), C.c_int32, P(C.c_double)]),
+    "clrrt_selftest_collision": (C.c_int, [C.c_void_p, C.c_int32, P(C.c_double), P(C.c_int32), C.c_int32,
+                                           P(C.c_double), P(C.c_uint32)]),
+    "clrrt_debug_grid": (C.c_int, [C.c_void_p, P(C.c_int32), P(C.c_float), P(C.c_uint32), P(C.c_uint16),
+                                   P(C.c_uint16)]),
     "clrrt_get_counters": (C.c_int, [C.c_void_p, P(abi.Counters)]),
     "clrrt_reset_counters": (C.c_int, [C.c_void_p]),
     "clrrt_work_counters": (C.c_int, [C.c_void_p, P(C.c_int64)]),
@@ -517,6 +521,43 @@ class Planner:
         self._chk(self.L.clrrt_obstacle_distance(self.h, x.ctypes.data_as(P(C.c_double)), x.shape[0],
                                                  out.ctypes.data_as(P(C.c_double))), "obstacle_distance")
         return out
+
+    # clrrt_selftest_collision paths (include/clrrt.h)
+    COLL_EXHAUSTIVE, COLL_LANE, COLL_LANE_NOGRID, COLL_COOP = 0, 1, 2, 3
+
+    def selftest_collision(self, path, states, active=None):
+        """The rollout kernels' collision decision for states [n, 10] (clrrt_selftest_collision) -> (dist [n],
+        tests [n]); active [n] (default all 1): 0 makes the state an idle lane (dist -1, tests 0)."""
+        x = np.ascontiguousarray(states, dtype=np.float64).reshape(-1, 10)
+        n = x.shape[0]
+        act = np.ones(n, dtype=np.int32) if active is None else np.ascontiguousarray(active, dtype=np.int32)
+        assert act.shape == (n,)
+        dist = np.zeros(n)
+        tests = np.zeros(n, dtype=np.uint32)
+        self._chk(self.L.clrrt_selftest_collision(self.h, path, x.ctypes.data_as(P(C.c_double)),
+                                                  act.ctypes.data_as(P(C.c_int32)), n,
+                                                  dist.ctypes.data_as(P(C.c_double)),
+                                                  tests.ctypes.data_as(P(C.c_uint32))), "selftest_collision")
+        return dist, tests
+
+    def grid_info(self, lists=True):
+        """The static-obstacle grid of the current obstacles (clrrt_debug_grid): gw, gh, x0, y0, inv, nitems, nmov,
+        coop (a rollout launch uses the wave-cooperative check), exempt (obstacles exempt from culling) and, with
+        lists, start [gw gh + 1], items [nitems], mov [nmov]."""
+        ii = (C.c_int32 * 6)()
+        ff = (C.c_float * 3)()
+        self._chk(self.L.clrrt_debug_grid(self.h, ii, ff, None, None, None), "debug_grid")
+        g = {"gw": ii[0], "gh": ii[1], "nitems": ii[2], "nmov": ii[3], "coop": bool(ii[4]), "exempt": ii[5],
+             "x0": np.float32(ff[0]), "y0": np.float32(ff[1]), "inv": np.float32(ff[2])}
+        if lists:
+            start = np.zeros(g["gw"] * g["gh"] + 1, dtype=np.uint32)
+            items = np.zeros(max(g["nitems"], 1), dtype=np.uint16)
+            mov = np.zeros(max(g["nmov"], 1), dtype=np.uint16)
+            self._chk(self.L.clrrt_debug_grid(self.h, ii, ff, start.ctypes.data_as(P(C.c_uint32)),
+                                              items.ctypes.data_as(P(C.c_uint16)),
+                                              mov.ctypes.data_as(P(C.c_uint16))), "debug_grid")
+            g.update(start=start if g["gw"] > 0 else start[:0], items=items[:g["nitems"]], mov=mov[:g["nmov"]])
+        return g
 
     def search_work(self):
         out = (C.c_int64 * 4)()

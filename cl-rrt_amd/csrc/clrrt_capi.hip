@@ -64,6 +64,7 @@ struct clrrt_ctx {
   ObsGrid grid{};              // device view of the static-obstacle grid
   void* grid_buf = nullptr;    // start | items | mov
   size_t grid_bytes = 0;
+  int grid_exempt = 0;         // obstacles exempt from culling (always-tested list, see build_grid)
   // round buffers (capacity cap.max_batch samples)
   clrrt_sample* d_samples = nullptr;
   float* pk = nullptr;
@@ -843,8 +844,14 @@ int clrrt_set_params(clrrt_ctx* c, const clrrt_params* p) {
 // cell size starts near 1/1024 of the covered area and grows until the grid fits the LDS budget.
 static const float kVehRad = 2.6220219f, kCullMargin = 0.05f;  // = VEH_RAD, CULL_MARGIN (kernels)
 static int build_grid(clrrt_ctx* c, const std::vector<BakedObs>& b) {
+  // `mov`: the obstacles tested at every step, ascending -- the moving ones and those exempt from culling
   std::vector<int> stat, mov;
-  for (int i = 0; i < (int)b.size(); i++) (b[i].moving ? mov : stat).push_back(i);
+  c->grid_exempt = 0;
+  for (int i = 0; i < (int)b.size(); i++) {
+    const bool exempt = std::isinf(b[i].brad);
+    c->grid_exempt += exempt;
+    (b[i].moving || exempt ? mov : stat).push_back(i);
+  }
   const double tol = 0.05;
   double x0 = 1e300, y0 = 1e300, x1 = -1e300, y1 = -1e300;
   std::vector<double> rr(b.size());
@@ -984,7 +991,15 @@ int clrrt_set_obstacles(clrrt_ctx* c, const clrrt_obstacle* o, int32_t m) {
   if (m > c->cap.max_obstacles) return fail(c, CLRRT_ECAPACITY, "too many obstacles");
   if (m > 1400) return fail(c, CLRRT_ECAPACITY, "at most 1400 obstacles (rollout LDS cull table)");
   std::vector<BakedObs> b(m);
-  for (int i = 0; i < m; i++) bake_obstacle(o[i], b[i]);
+  for (int i = 0; i < m; i++) {
+    bake_obstacle(o[i], b[i]);
+    // beyond CULL_EXEMPT_BOUND the culls' margin no longer covers the float rounding of the reference's SAT: such an
+    // obstacle is never culled (a non-finite one neither)
+    const double reach = std::max(std::fabs(o[i].cx) + std::fabs(o[i].vx) * CULL_EXEMPT_HORIZON,
+                                  std::fabs(o[i].cy) + std::fabs(o[i].vy) * CULL_EXEMPT_HORIZON) +
+                         (double)b[i].brad + 16.0;
+    if (!(reach < CULL_EXEMPT_BOUND)) b[i].brad = INFINITY;
+  }
   HIPC(c, hipSetDevice(c->device));
   int frc = flush_replays(c);  // pending replays collide against the obstacles they were committed with
   if (frc != CLRRT_OK) return frc;
@@ -3699,6 +3714,60 @@ int clrrt_selftest_units(clrrt_ctx* c, int32_t unit, const double* in, int32_t n
   if (dobs) hipFree(dobs);
   if (dcp) hipFree(dcp);
   if (e != hipSuccess) return fail(c, CLRRT_EHIP, std::string("selftest_units: ") + hipGetErrorString(e));
+  return CLRRT_OK;
+}
+
+int clrrt_selftest_collision(clrrt_ctx* c, int32_t path, const double* states, const int32_t* active, int32_t n,
+                             double* dist, uint32_t* tests) {
+  if (!c || n < 0 || (n > 0 && (!states || !active || !dist || !tests)) || path < CLRRT_COLL_EXHAUSTIVE ||
+      path > CLRRT_COLL_COOP)
+    return CLRRT_EINVAL;
+  RollArgs a = roll_args(c, 0);
+  a.ctr = nullptr;
+  a.coop_enable = c->roll_coop;
+  if (path == CLRRT_COLL_COOP && !roll_coop_applies(a))
+    return fail(c, CLRRT_EINVAL, "selftest_collision: a rollout launch would not use the cooperative check here");
+  HIPC(c, hipSetDevice(c->device));
+  if (n == 0) return CLRRT_OK;
+  double *din = nullptr, *ddist = nullptr;
+  int32_t* dact = nullptr;
+  uint32_t* dtests = nullptr;
+  hipError_t e = hipMalloc((void**)&din, sizeof(double) * 10 * (size_t)n);
+  if (e == hipSuccess) e = hipMalloc((void**)&ddist, sizeof(double) * (size_t)n);
+  if (e == hipSuccess) e = hipMalloc((void**)&dact, sizeof(int32_t) * (size_t)n);
+  if (e == hipSuccess) e = hipMalloc((void**)&dtests, sizeof(uint32_t) * (size_t)n);
+  if (e == hipSuccess) e = hipMemcpyAsync(din, states, sizeof(double) * 10 * (size_t)n, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(dact, active, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = launch_selftest_collision(c->stream, a, path, din, dact, n, ddist, dtests);
+  if (e == hipSuccess) e = hipMemcpyAsync(dist, ddist, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(tests, dtests, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  hipFree(din);
+  hipFree(ddist);
+  hipFree(dact);
+  hipFree(dtests);
+  if (e != hipSuccess) return fail(c, CLRRT_EHIP, std::string("selftest_collision: ") + hipGetErrorString(e));
+  return CLRRT_OK;
+}
+
+int clrrt_debug_grid(clrrt_ctx* c, int32_t info_i[6], float info_f[3], uint32_t* start, uint16_t* items,
+                     uint16_t* mov) {
+  if (!c || !info_i || !info_f) return CLRRT_EINVAL;
+  const ObsGrid& g = c->grid;
+  RollArgs a = roll_args(c, 0);
+  a.coop_enable = c->roll_coop;
+  info_i[0] = g.gw; info_i[1] = g.gh; info_i[2] = g.nitems; info_i[3] = g.nmov;
+  info_i[4] = roll_coop_applies(a) ? 1 : 0;
+  info_i[5] = c->grid_exempt;
+  info_f[0] = g.x0; info_f[1] = g.y0; info_f[2] = g.inv;
+  HIPC(c, hipSetDevice(c->device));
+  if (start && g.gw > 0)
+    HIPC(c, hipMemcpyAsync(start, g.start, sizeof(uint32_t) * ((size_t)g.gw * g.gh + 1), hipMemcpyDeviceToHost, c->stream));
+  if (items && g.nitems > 0)
+    HIPC(c, hipMemcpyAsync(items, g.items, sizeof(uint16_t) * (size_t)g.nitems, hipMemcpyDeviceToHost, c->stream));
+  if (mov && g.nmov > 0)
+    HIPC(c, hipMemcpyAsync(mov, g.mov, sizeof(uint16_t) * (size_t)g.nmov, hipMemcpyDeviceToHost, c->stream));
+  HIPC(c, hipStreamSynchronize(c->stream));
   return CLRRT_OK;
 }
 

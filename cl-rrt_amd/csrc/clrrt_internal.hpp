@@ -78,6 +78,11 @@ struct SimJob {
 // Uniform grid over the static obstacles (built on the host by clrrt_set_obstacles): cell
 // (gx, gy) lists, ascending, every static obstacle whose inflated bounding circle (radius + vehicle
 // radius + margin, the kernel's cull test) comes within a small tolerance of the cell.
+// An obstacle that can come within 16 m of CULL_EXEMPT_BOUND (either coordinate) during CULL_EXEMPT_HORIZON seconds
+// of prediction is exempt from culling (derivation beside CULL_MARGIN, clrrt_kernels.hip): brad = INFINITY in its
+// BakedObs, listed in `mov`.
+#define CULL_EXEMPT_BOUND 32768.0
+#define CULL_EXEMPT_HORIZON 3600.0
 struct ObsGrid {
   const uint32_t* start;  // [gw*gh + 1]
   const uint16_t* items;
@@ -387,6 +392,12 @@ hipError_t launch_append(hipStream_t st, const clrrt_node* in, int n, int64_t ba
 hipError_t launch_selftest_math(hipStream_t st, int fn, const double* a, const double* b, int n, double* out);
 hipError_t launch_obs_distance(hipStream_t st, const DevParams& p, const BakedObs* obs, const double* states, int n,
                                double* out);
+// Whether launch_rollout_persistent runs the wave-cooperative collision check (k_roll_run<_, true, _>) for these
+// arguments: option roll_coop, OBB collision without the gap value, a static grid, and LDS room for the scratch.
+bool roll_coop_applies(const RollArgs& a);
+// clrrt_selftest_collision: path CLRRT_COLL_* for n states (10 doubles each) with their active flags
+hipError_t launch_selftest_collision(hipStream_t st, const RollArgs& a, int path, const double* states,
+                                     const int32_t* active, int n, double* dist, uint32_t* tests);
 // cp: per-case parameters (units CLRRT_UNIT_FEASIBLE .. CLRRT_UNIT_CTRL), else null
 hipError_t launch_selftest_units(hipStream_t st, int unit, const double* in, const BakedObs* obs, int n,
                                  const DevParams& p, const DevParams* cp, double* out);

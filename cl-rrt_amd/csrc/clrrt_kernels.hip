@@ -793,6 +793,24 @@ struct ObsView {
 
 #define VEH_RAD 2.6220219f  /* sqrt(2.424^2 + 1^2), vehicle half-diagonal */
 #define CULL_MARGIN 0.05f
+// What the margin has to cover.  A cull may discard an obstacle only where the reference's SAT -- float vertices,
+// float projections -- cannot report overlap.  The culls keep every obstacle whose exact box comes within
+// CULL_MARGIN of the vehicle's bounding circle (the grid's cell lists: within a further tol = 0.05 m).  With every
+// coordinate of the decision below C in magnitude and u = ulp(C) = C 2^-24 (float):
+//   - the reference rounds each vertex to float (<= u / sqrt 2), so it tests two convex quadrilaterals whose
+//     distance is >= m - 1.5 u when the exact boxes are m apart; some edge normal of theirs separates them by
+//     >= (m - 1.5 u) / sqrt 2 (vertex against vertex is the worst case of near-rectangles);
+//   - it evaluates that gap as the difference of two float projections v . n with |v| <= sqrt 2 C, three
+//     roundings each: <= 3 sqrt 2 u per projection in units of distance, 8.5 u for the pair;
+//   - the culls round the two centres to float and do their own float arithmetic on the (small) differences: <= 2 u.
+// No overlap is reported, and the cull is sound, while (m - 1.5 u) / sqrt 2 > 10.5 u, i.e. m > 16.4 u.  With
+// m = CULL_MARGIN = 50 mm that needs u <= 3.05 mm: u = 2^-9 m (1.95 mm) for C = CULL_EXEMPT_BOUND = 2^15 m holds
+// with 18 mm to spare, u = 2^-8 m (C = 2^16 m) does not.  (Measured errors are 1..3 u: the first false discards
+// appear at 2^18 m, tests/test_collision_cull.py.)  clrrt_set_obstacles therefore exempts from culling every
+// obstacle that can come within 16 m (the vehicle box and the margins) of that bound during CULL_EXEMPT_HORIZON
+// seconds of prediction: brad = inf in its baked record, hence an infinite radius and infinite half extents in the
+// tables below, and a place in the always-tested list beside the moving obstacles (build_grid); its SAT is
+// obs_sat_baked as ever.  Below the bound nothing changes.  (The two constants: clrrt_internal.hpp.)
 
 // One obstacle against the vehicle box: bounding-circle cull (no overlap possible when the
 // circles are apart), then the SAT gap.
@@ -1265,7 +1283,8 @@ __device__ __forceinline__ ObsView stage_obstacles(const RollArgs& a, float4* ld
       // box axes from the baked products: P = cos*hh, R = sin*hh, Q = sin*ww, S = cos*ww
       const float hh = sqrtf(o.P * o.P + o.R * o.R), ww = sqrtf(o.Q * o.Q + o.S * o.S);
       const float ux = hh > 0.f ? o.P / hh : 1.f, uy = hh > 0.f ? o.R / hh : 0.f;
-      ob[j] = make_float4(ux, uy, hh * 1.00001f + 1e-4f, ww * 1.00001f + 1e-4f);
+      const bool exempt = o.brad == INFINITY;  // never culled (CULL_EXEMPT_BOUND)
+      ob[j] = make_float4(ux, uy, exempt ? INFINITY : hh * 1.00001f + 1e-4f, exempt ? INFINITY : ww * 1.00001f + 1e-4f);
       sat[4 * j] = make_float4(o.vx[0], o.vx[1], o.vx[2], o.vx[3]);
       sat[4 * j + 1] = make_float4(o.vy[0], o.vy[1], o.vy[2], o.vy[3]);
       sat[4 * j + 2] = make_float4(o.nx[0], o.nx[1], o.nx[2], o.nx[3]);
@@ -2923,10 +2942,56 @@ __global__ void k_obs_distance(DevParams p, const BakedObs* __restrict__ obs, co
   out[i] = obs_distance<true>(r, p, ov, tests);
 }
 
+// Test hook (clrrt_selftest_collision): the rollout kernels' collision decision for explicit states, one state
+// per lane (state i = lane i % 64 of wave i / 64), through the device functions the step loops call.  The LDS
+// holds what k_roll_run's holds: the obstacle tables (stage_obstacles<false>) and, at a.coop_off, each wave's
+// cooperative scratch.  Control flow is wave-uniform up to the collision call (obs_distance_coop is entered by
+// every lane of the wave, a lane without a state or with active 0 as act = false).
+__global__ void __launch_bounds__(256) k_selftest_collision(RollArgs a, int path, const double* __restrict__ st,
+                                                            const int32_t* __restrict__ active, int n,
+                                                            double* __restrict__ dist, uint32_t* __restrict__ tests) {
+  extern __shared__ float4 lds[];
+  glibc::stage_tables();
+  ObsView ov{a.obs, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+             a.p.coll_mode == CLRRT_COLLISION_OBB ? a.p.n_obs : 0, 0, 0, 0, 0.f, 0.f, 0.f};
+  if (path != CLRRT_COLL_EXHAUSTIVE) ov = stage_obstacles<false>(a, lds);
+  if (path == CLRRT_COLL_LANE_NOGRID) ov.gw = ov.gh = 0;
+  CLRRT_PARAMS_DECL(P);
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool act = i < n && active[i] != 0;
+  Roll r;
+  r.x0 = r.x1 = r.x2 = r.x6 = 0.0;
+  r.s2 = 0.0; r.c2 = 1.0;
+  if (act) {
+    const double* x = st + 10 * (int64_t)i;
+    r.x0 = x[0]; r.x1 = x[1]; r.x2 = x[2]; r.x6 = x[6];
+    glibc::sincos(r.x2, r.s2, r.c2);
+  }
+  uint32_t cnt = 0;
+  double D = -1.0;  // a lane without an active state
+  if (path == CLRRT_COLL_COOP) {
+    CoopLds cl{};
+    char* base = (char*)lds + a.coop_off + (size_t)(threadIdx.x >> 6) * kCoopLdsPerWave;
+    cl.veh = (Box4*)base;
+    cl.t = (double*)(base + 64 * sizeof(Box4));
+    cl.hit = (int*)(base + 64 * sizeof(Box4) + 64 * sizeof(double));
+    cl.q = (uint32_t*)(base + 64 * sizeof(Box4) + 64 * sizeof(double) + 64 * sizeof(int));
+    cl.cap = COOP_QCAP;
+    const double Dc = obs_distance_coop(act, r, P, ov, cnt, cl);
+    if (act) D = Dc;
+  } else if (act) {
+    D = path == CLRRT_COLL_EXHAUSTIVE ? obs_distance<true>(r, P, ov, cnt) : obs_distance<false>(r, P, ov, cnt);
+  }
+  if (i < n) {
+    dist[i] = D;
+    tests[i] = cnt;
+  }
+}
+
 // ============================================================================================
 // launch wrappers (host)
 // ============================================================================================
-#define LAUNCH_CHECK()                                   \
+#define LAUNCH_CHECK()                                  \
   do {                                                   \
     hipError_t e__ = hipGetLastError();                  \
     if (e__ != hipSuccess) return e__;                   \
@@ -3119,6 +3184,15 @@ static size_t roll_lds_bytes(const RollArgs& a) {
   return lds;
 }
 
+// dynamic LDS of k_roll_run: the obstacle tables (not with NEED_GAP), then (COOP) the cooperative
+// collision check's per-wave scratch, when the static grid is built and the whole fits the 160 KB a
+// workgroup may use beside the glibc tables' static LDS (~12 KB)
+static size_t roll_obs_lds(const RollArgs& a) { return a.p.need_gap ? 0 : (roll_lds_bytes(a) + 15) / 16 * 16; }
+bool roll_coop_applies(const RollArgs& a) {
+  return a.coop_enable && !a.p.need_gap && a.p.coll_mode == CLRRT_COLLISION_OBB && a.p.n_obs > 0 && a.grid.gw > 0 &&
+         roll_obs_lds(a) + 4 * kCoopLdsPerWave <= 148 * 1024;
+}
+
 template <int SRC>
 static hipError_t launch_roll_t(hipStream_t st, const RollArgs& a) {
   if (a.njobs <= 0) return hipSuccess;
@@ -3183,12 +3257,8 @@ hipError_t launch_rollout_persistent(hipStream_t st, const RollArgs& a0, int B, 
   }
   RollArgs a = a0;
   a.B = B;
-  // dynamic LDS of k_roll_run: the obstacle tables (not with NEED_GAP), then (COOP) the cooperative
-  // collision check's per-wave scratch, when the static grid is built and the whole fits the 160 KB a
-  // workgroup may use beside the glibc tables' static LDS (~12 KB)
-  const size_t obs_lds = a.p.need_gap ? 0 : (roll_lds_bytes(a0) + 15) / 16 * 16;
-  const bool coop = a.coop_enable && !a.p.need_gap && a.p.coll_mode == CLRRT_COLLISION_OBB && a.p.n_obs > 0 && a.grid.gw > 0 &&
-                    obs_lds + 4 * kCoopLdsPerWave <= 148 * 1024;
+  const size_t obs_lds = roll_obs_lds(a0);
+  const bool coop = roll_coop_applies(a);
   a.coop_off = (int)obs_lds;
   const size_t lds = obs_lds + (coop ? 4 * kCoopLdsPerWave : 0);
   const bool carry = a.cap > 0 || a.ncarry > 0;  // deferred samples: the CARRY instantiation
@@ -3398,6 +3468,24 @@ hipError_t launch_obs_distance(hipStream_t st, const DevParams& p, const BakedOb
                                double* out) {
   if (n <= 0) return hipSuccess;
   hipLaunchKernelGGL(k_obs_distance, dim3((n + 255) / 256), dim3(256), 0, st, p, obs, states, n, out);
+  LAUNCH_CHECK();
+  return hipSuccess;
+}
+
+hipError_t launch_selftest_collision(hipStream_t st, const RollArgs& a0, int path, const double* states,
+                                     const int32_t* active, int n, double* dist, uint32_t* tests) {
+  if (n <= 0) return hipSuccess;
+  RollArgs a = a0;
+  // the LDS of k_roll_run (launch_rollout_persistent): obstacle tables, then the four waves' cooperative scratch
+  const size_t obs_lds = path == CLRRT_COLL_EXHAUSTIVE ? 0 : (roll_lds_bytes(a) + 15) / 16 * 16;
+  a.coop_off = (int)obs_lds;
+  const size_t lds = obs_lds + (path == CLRRT_COLL_COOP ? 4 * kCoopLdsPerWave : 0);
+  hipError_t e;
+  if (lds > 64 * 1024 && (e = hipFuncSetAttribute((const void*)&k_selftest_collision,
+                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != hipSuccess)
+    return e;
+  hipLaunchKernelGGL(k_selftest_collision, dim3((n + 255) / 256), dim3(256), lds, st, a, path, states, active, n, dist,
+                     tests);
   LAUNCH_CHECK();
   return hipSuccess;
 }

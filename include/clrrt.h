@@ -217,6 +217,9 @@ void clrrt_destroy(clrrt_ctx* ctx);
 const char* clrrt_last_error(const clrrt_ctx* ctx);
 int clrrt_set_stream(clrrt_ctx* ctx, void* hip_stream);
 int clrrt_set_params(clrrt_ctx* ctx, const clrrt_params* p);
+/* Obstacles may lie at any finite coordinates.  The rollouts cull obstacles that cannot reach the vehicle; one whose
+ * centre, moved by 3600 s of its velocity, plus its bounding radius and 16 m reaches 2^15 m in either coordinate is
+ * exempt from culling (tested at every step): out there a float ulp is no longer small against the culls' margin. */
 int clrrt_set_obstacles(clrrt_ctx* ctx, const clrrt_obstacle* obs, int32_t m);
 int clrrt_set_rank(clrrt_ctx* ctx, int32_t rank);
 
@@ -498,6 +501,30 @@ int clrrt_selftest_math(clrrt_ctx* ctx, int32_t fn, const double* a, const doubl
 #define CLRRT_UNIT_PROFILE_NMAX 1024
 #define CLRRT_UNIT_CTRL_K 24
 int clrrt_selftest_units(clrrt_ctx* ctx, int32_t unit, const double* in, int32_t n, double* out);
+/* Test hook: the rollout kernels' collision decision (checkObsDistance, old_collisioncheck.cpp:24-51) for n
+ * explicit states (10 doubles each: x, y, heading in columns 0..2, t in column 6), by the device functions the
+ * step loops call, on the obstacle tables and grid staged in LDS as the rollout kernels stage them.  path:
+ *   CLRRT_COLL_EXHAUSTIVE   every obstacle, gap value kept (what clrrt_obstacle_distance runs)
+ *   CLRRT_COLL_LANE         one lane per state over the static grid's cell list merged with the moving
+ *                           obstacles (the linear scan behind the culls where the query has no grid)
+ *   CLRRT_COLL_LANE_NOGRID  the same with the grid withheld: the linear scan behind the culls
+ *   CLRRT_COLL_COOP         the wave-cooperative check of the persistent rollout kernel: state i is lane i % 64 of
+ *                           wave i / 64; CLRRT_EINVAL where a rollout launch would not use it (option roll_coop 0,
+ *                           no static grid, collision mode or cost terms that need the gap value)
+ * active[i] = 0 makes state i an idle lane of its wave (dist -1, tests 0).  dist[i]: the value the step would
+ * get (0 = collision); tests[i]: what the call adds to the box-test work counter (clrrt_work_counters out[2]). */
+#define CLRRT_COLL_EXHAUSTIVE 0
+#define CLRRT_COLL_LANE 1
+#define CLRRT_COLL_LANE_NOGRID 2
+#define CLRRT_COLL_COOP 3
+int clrrt_selftest_collision(clrrt_ctx* ctx, int32_t path, const double* states, const int32_t* active, int32_t n,
+                             double* dist, uint32_t* tests);
+/* Test hook: the static-obstacle grid of the current obstacles.  info_i = gw, gh (0, 0: no grid), items, moving
+ * obstacles (with the static ones exempt from culling, see clrrt_set_obstacles), 1 when a rollout launch uses the
+ * wave-cooperative check, the obstacles exempt from culling; info_f = origin x, y, 1 / cell size.  start
+ * (gw gh + 1 entries), items, mov (the always-tested ids, ascending) are copied where non-NULL. */
+int clrrt_debug_grid(clrrt_ctx* ctx, int32_t info_i[6], float info_f[3], uint32_t* start, uint16_t* items,
+                     uint16_t* mov);
 
 int clrrt_get_counters(clrrt_ctx* ctx, clrrt_counters* out);
 int clrrt_reset_counters(clrrt_ctx* ctx);

@@ -1081,6 +1081,23 @@ double orc_check_obs(void* h, const double* x10) {
   return obs_distance(*o, x);
 }
 
+// checkObsDistance for n states (10 doubles each): dist[i] as orc_check_obs, first[i] the index of the first
+// obstacle whose getOBBdist is 0 (where the reference's loop returns; -1: none).  The reference's box-test
+// count of the state is first + 1 on a hit, else the obstacle count.
+void orc_check_obs_n(void* h, const double* states, long n, double* dist, int* first) {
+  Oracle* o = (Oracle*)h;
+  for (long i = 0; i < n; i++) {
+    std::vector<double> x(states + 10 * i, states + 10 * i + 10);
+    dist[i] = obs_distance(*o, x);
+    first[i] = -1;
+    if (o->p.collision_mode == CLRRT_COLLISION_STUB) continue;
+    const double t = o->p.obs_use_pred ? x[6] : 0;
+    const Box veh = veh_box(x);
+    for (size_t j = 0; j != o->det.size(); j++)
+      if (box_gap(veh, obs_box(o->det[j], t)) == 0) { first[i] = (int)j; break; }
+  }
+}
+
 // Draw `n` iterations' samples from glibc rand() in the reference order (rLong, rLat, r).
 void orc_draw_samples(void* h, int n, double* xy, int* explore) {
   Oracle* o = (Oracle*)h;

@@ -51,6 +51,7 @@ def lib():
             "orc_dubins": (f, [vp, d, d, l]),
             "orc_obb_dist": (d, [d, d, f, f, f, d, d, f, f, f]),
             "orc_check_obs": (d, [vp, P(d)]),
+            "orc_check_obs_n": (None, [vp, P(d), l, P(d), P(i)]),
             "orc_draw_samples": (None, [vp, i, P(d), P(i)]),
             "orc_eval_iteration": (i, [vp, d, d, i, i, P(abi.Node)]),
             "orc_eval_iterations": (None, [vp, i, P(C.c_double), P(C.c_double), P(C.c_int), i, i, P(abi.Node),
@@ -213,6 +214,15 @@ class Oracle:
     def check_obs(self, x10):
         x = np.ascontiguousarray(x10, dtype=np.float64)
         return self.L.orc_check_obs(self.h, _dp(x))
+
+    def check_obs_n(self, states):
+        """checkObsDistance for states [n, 10] -> (dist [n], first [n]): first = index of the first overlapping
+        obstacle, -1 without one (the reference tests first + 1 boxes on a hit, else every obstacle)."""
+        x = np.ascontiguousarray(states, dtype=np.float64).reshape(-1, 10)
+        dist = np.zeros(x.shape[0])
+        first = np.zeros(x.shape[0], dtype=np.int32)
+        self.L.orc_check_obs_n(self.h, _dp(x), x.shape[0], _dp(dist), first.ctypes.data_as(C.POINTER(C.c_int)))
+        return dist, first
 
     def draw_samples(self, n):
         xy = np.zeros(2 * n)

@@ -52,6 +52,7 @@ _SIGS = {
     "clrrt_path_commit": (C.c_int, [C.c_void_p, P(C.c_int32), C.c_int32, P(C.c_int32)]),
     "clrrt_path_load": (C.c_int, [C.c_void_p, P(abi.Node), C.c_int32, P(C.c_double), C.c_int64]),
     "clrrt_path_size": (C.c_int, [C.c_void_p, P(C.c_int32), P(C.c_int64)]),
+    "clrrt_path_device": (C.c_int, [C.c_void_p, P(C.c_void_p), P(P(C.c_double)), P(C.c_int32), P(C.c_int64)]),
     "clrrt_path_download": (C.c_int, [C.c_void_p, P(abi.Node), P(C.c_double)]),
     "clrrt_path_transform": (C.c_int, [C.c_void_p, C.c_int32, P(C.c_double)]),
     "clrrt_tree_init_from_path": (C.c_int, [C.c_void_p, P(C.c_double), P(C.c_int32)]),

@@ -197,6 +197,10 @@ def xchg_lib():
             "clrrt_xchg_records": (C.c_void_p, [C.c_void_p]),
             "clrrt_xchg_stats": (C.c_int, [C.c_void_p, P(C.c_int64)]),
             "clrrt_xchg_destroy": (None, [C.c_void_p]),
+            "clrrt_xchg_path_rows": (C.c_int32, [C.c_void_p, C.c_void_p, P(C.c_int64)]),
+            "clrrt_xchg_path_stats": (C.c_int, [C.c_void_p, P(C.c_int64)]),
+            "clrrt_xchg_selftest_path_select": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, P(C.c_int32),
+                                                          P(C.c_int32), C.c_void_p, P(C.c_int64)]),
             "clrrt_xchg_selftest_concat": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, P(C.c_int32), P(C.c_double),
                                                      P(C.c_int64), P(C.c_double), C.c_int32, C.c_void_p, C.c_int64,
                                                      P(C.c_int64)]),
@@ -259,6 +263,25 @@ class NativeExchange:
         self.L.clrrt_xchg_stats(self.h, out)
         keys = ("exchanges", "collectives", "second_gathers", "closing", "rows_sent", "rows_received", "bound")
         return dict(zip(keys, (int(v) for v in out)))
+
+    def path_rows(self, planner):
+        """Complete the committed path's rows across the ranks on the device (clrrt_xchg_path_rows): collective,
+        after planner.path_commit on every rank and before path_transform.  Returns the rows this rank took from
+        other ranks.  (fetch_path_rows is the same through torch.distributed and the host.)"""
+        import ctypes as C
+        from . import ClrrtError
+        moved = C.c_int64(0)
+        rc = self.L.clrrt_xchg_path_rows(self.h, planner.h, C.byref(moved))
+        if rc != 0:
+            raise ClrrtError(f"clrrt_xchg_path_rows -> {rc}: {self.L.clrrt_xchg_last_error().decode()}")
+        return int(moved.value)
+
+    def path_stats(self):
+        """completions, collectives, rows gathered, rows taken (clrrt_xchg_path_stats)."""
+        import ctypes as C
+        out = (C.c_int64 * 4)()
+        self.L.clrrt_xchg_path_stats(self.h, out)
+        return dict(zip(("completions", "collectives", "rows_gathered", "rows_taken"), (int(v) for v in out)))
 
     rounds = property(lambda self: self.stats()["exchanges"])
     collectives = property(lambda self: self.stats()["collectives"])

@@ -63,11 +63,16 @@ def advance_pose(pose, path_rows, dt=QUERY_PERIOD):
 
 
 class PlannerBackend:
-    """The five planMotion steps on the HIP planner (clrrt.Planner)."""
+    """The five planMotion steps on the HIP planner (clrrt.Planner).  complete_path: with a sharded planner, the
+    collective that completes the committed path's rows across the ranks, called in every query between path_commit
+    and path_transform with the planner (clrrt.dist.NativeExchange.path_rows, or
+    lambda pl: clrrt.dist.fetch_path_rows(pl, rank)); its result (rows moved) is kept in rows_fetched."""
 
-    def __init__(self, planner, make_params):
+    def __init__(self, planner, make_params, complete_path=None):
         self.pl = planner
         self.make_params = make_params
+        self.complete_path = complete_path
+        self.rows_fetched = 0
 
     def begin_query(self, pose, goal_car, obs_car):
         self.pl.set_params(self.make_params(pose[4], goal_car))
@@ -78,6 +83,8 @@ class PlannerBackend:
     def end_query(self, pose):
         ids, _, _ = self.pl.extract_best_path()
         self.pl.path_commit(ids)
+        if self.complete_path is not None:
+            self.rows_fetched = self.complete_path(self.pl)
         self.pl.path_transform(True, pose)
         _, rows = self.pl.path_download()
         return ids, rows

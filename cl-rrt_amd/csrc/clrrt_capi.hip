@@ -1271,6 +1271,15 @@ int clrrt_path_size(clrrt_ctx* c, int32_t* n, int64_t* n_rows) {
   return CLRRT_OK;
 }
 
+int clrrt_path_device(clrrt_ctx* c, void** dev_nodes, double** dev_rows, int32_t* n, int64_t* n_rows) {
+  if (!c) return CLRRT_EINVAL;
+  if (dev_nodes) *dev_nodes = c->path_n > 0 ? (void*)c->path_nodes : nullptr;
+  if (dev_rows) *dev_rows = c->path_n > 0 ? c->path_rows : nullptr;
+  if (n) *n = c->path_n;
+  if (n_rows) *n_rows = c->path_nrows;
+  return CLRRT_OK;
+}
+
 int clrrt_path_download(clrrt_ctx* c, clrrt_node* nodes, double* rows) {
   if (!c) return CLRRT_EINVAL;
   HIPC(c, hipSetDevice(c->device));

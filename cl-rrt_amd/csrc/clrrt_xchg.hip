@@ -1,6 +1,7 @@
 // libclrrt_xchg.so — the native exchange of the sharded expansion (include/clrrt_xchg.h): RoundExchange's
 // count-prefixed all-gather (clrrt/dist.py) behind clrrt_set_shards' hook, over RCCL (one process per GPU) or over an
-// in-process rendezvous with peer copies (one thread per rank), and the kernel both share, k_xchg_concat.
+// in-process rendezvous with peer copies (one thread per rank), and the kernel both share, k_xchg_concat; and the
+// completion of the committed path's rows across the ranks (clrrt_xchg_path_rows, k_xchg_path_select).
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
@@ -136,6 +137,87 @@ hipError_t launch_concat(hipStream_t st, const ConcatArgs& a, int64_t rows_per_p
   return hipGetLastError();
 }
 
+// ---- the committed path's rows (clrrt_xchg_path_rows)
+constexpr int PROW_V = 5;      // 16-byte vectors per trajectory row (10 doubles)
+constexpr int PROW = 80;       // bytes per trajectory row
+constexpr int PHDR = 148;      // clrrt_node bytes before owner / row_offset: what the ranks must agree on
+constexpr int PSEL_CHUNK = 256;  // path nodes a block holds in LDS at a time (one per thread)
+
+// what the ranks compare before any row moves
+struct PathHdr {
+  int64_t n, rows;
+  uint64_t hash;  // FNV-1a over the n headers' first PHDR bytes
+  int64_t pad;
+};
+static_assert(sizeof(PathHdr) == 32, "agreement record");
+
+struct PathSelectArgs {
+  const uint4* parts;        // [W][rows] trajectory rows: every rank's whole path row buffer (zeros where foreign)
+  uint4* dst;                // this rank's path rows
+  const clrrt_node* nodes;   // this rank's n path headers (path-local row_offset, its own view of owner)
+  int64_t rows;              // R
+  int n, W, self;
+};
+
+// One launch per completion on the engine's stream.  The path's nodes are taken PSEL_CHUNK at a time: thread t loads
+// node c0 + t's row range [start, end) and owner into LDS (clamped to [0, R] and start <= end, so nothing below can
+// index outside the buffers whatever the header holds), then the grid strides over the 16-byte vectors of the
+// chunk's rows -- 5 per 80-byte row, consecutive lanes consecutive vectors, so a wave's access is one contiguous
+// 1 KiB although node borders fall inside it -- and each vector finds its node by a binary search over the chunk's
+// starts (the last node whose start is <= the vector's row).  A vector of a node owned by another rank is copied
+// from that rank's part, as raw bits; a node this rank owns (or whose owner is no rank) is left alone.
+__global__ __launch_bounds__(256) void k_xchg_path_select(PathSelectArgs a) {
+  __shared__ int64_t s_start[PSEL_CHUNK];
+  __shared__ int64_t s_end[PSEL_CHUNK];
+  __shared__ int s_own[PSEL_CHUNK];
+  const int t = threadIdx.x;
+  const int64_t gtid = (int64_t)blockIdx.x * blockDim.x + t;
+  const int64_t gstride = (int64_t)gridDim.x * blockDim.x;
+  for (int c0 = 0; c0 < a.n; c0 += PSEL_CHUNK) {
+    const int cnt = a.n - c0 < PSEL_CHUNK ? a.n - c0 : PSEL_CHUNK;
+    __syncthreads();  // the last chunk's searches are done
+    if (t < cnt) {
+      const clrrt_node* nd = a.nodes + c0 + t;
+      int64_t s = nd->row_offset, e = nd->row_offset + (int64_t)nd->nrows;
+      s = s < 0 ? 0 : (s > a.rows ? a.rows : s);
+      e = e < s ? s : (e > a.rows ? a.rows : e);
+      s_start[t] = s;
+      s_end[t] = e;
+      s_own[t] = nd->owner;
+    }
+    __syncthreads();
+    const int64_t lo = s_start[0], hi = s_end[cnt - 1];
+    for (int64_t v = lo * PROW_V + gtid; v < hi * PROW_V; v += gstride) {
+      const int64_t row = v / PROW_V;
+      int i = 0, j = cnt - 1;  // the last node of the chunk whose start is <= row
+      while (i < j) {
+        const int m = (i + j + 1) >> 1;
+        if (s_start[m] <= row) i = m;
+        else j = m - 1;
+      }
+      const int own = s_own[i];
+      if (row >= s_start[i] && row < s_end[i] && own != a.self && own >= 0 && own < a.W)
+        a.dst[v] = a.parts[(int64_t)own * a.rows * PROW_V + v];
+    }
+  }
+}
+
+hipError_t launch_path_select(hipStream_t st, const PathSelectArgs& a) {
+  const int64_t vec = std::max<int64_t>(1, a.rows * PROW_V);
+  const int blocks = (int)std::min<int64_t>(256, (vec + 255) / 256);
+  hipLaunchKernelGGL(k_xchg_path_select, dim3(blocks), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+uint64_t path_hash(const clrrt_node* h, int n) {
+  uint64_t x = 0xcbf29ce484222325ull;
+  for (int i = 0; i < n; i++) {
+    const unsigned char* b = (const unsigned char*)&h[i];
+    for (int k = 0; k < PHDR; k++) x = (x ^ b[k]) * 0x100000001b3ull;
+  }
+  return x;
+}
+
 thread_local std::string t_err;
 int fail(int code, const std::string& msg) {
   t_err = msg;
@@ -170,6 +252,9 @@ const char* nccl_name(ncclResult_t r) {
 struct LocalSlot {
   clrrt_xchg* x = nullptr;
   int closing = 0;  // this exchange is the rank's closing one
+  // the path completion: this rank's agreement record and its path row buffer (R rows)
+  PathHdr path{};
+  const char* path_rows = nullptr;
 };
 
 struct clrrt_xchg_group {
@@ -198,6 +283,17 @@ struct clrrt_xchg {
   hipEvent_t ev_sent = nullptr;    // this rank's rows are written (peers wait for it before pulling)
   hipEvent_t ev_pulled = nullptr;  // this rank's pulls are done (the owners wait for it before going on)
   int64_t st[8] = {};
+  // the path completion (clrrt_xchg_path_rows)
+  clrrt_ctx* ctx = nullptr;        // the attached context
+  hipStream_t stream = nullptr;    // its stream, as the last exchange saw it
+  bool have_stream = false;
+  clrrt_node* h_nodes = nullptr;   // pinned: this rank's path headers
+  int h_nodes_cap = 0;
+  char* p_recv = nullptr;          // [world][R] trajectory rows, grown on demand
+  int64_t p_recv_rows = 0;         // rows it holds
+  PathHdr* d_phdr = nullptr;       // RCCL: [1 + world] agreement records (this rank's, then the gathered ones)
+  PathHdr* h_phdr = nullptr;       // pinned [1 + world]
+  int64_t pst[4] = {};
 };
 
 namespace {
@@ -213,6 +309,8 @@ int alloc_common(clrrt_xchg* x) {
   XHIP(hipHostMalloc((void**)&x->h_sum, sizeof(Summary), hipHostMallocDefault));
   XHIP(hipHostMalloc((void**)&x->h_hdr, sizeof(Header), hipHostMallocDefault));
   XHIP(hipEventCreateWithFlags(&x->ev_sum, hipEventDisableTiming));
+  XHIP(hipMalloc((void**)&x->d_phdr, sizeof(PathHdr) * (1 + x->world)));
+  XHIP(hipHostMalloc((void**)&x->h_phdr, sizeof(PathHdr) * (1 + x->world), hipHostMallocDefault));
   return CLRRT_OK;
 }
 
@@ -342,11 +440,197 @@ int hook_local(clrrt_xchg* x, clrrt_exchange_io* io, hipStream_t st, bool closin
   return CLRRT_OK;
 }
 
+// ---- the path completion
+struct PathView {
+  clrrt_node* d_nodes = nullptr;
+  double* d_rows = nullptr;
+  int32_t n = 0;
+  int64_t rows = 0;
+  int64_t moved = 0;          // rows of the nodes another rank owns
+  bool need[MAXW] = {};       // ranks that own a node of the path (other than this rank)
+};
+
+int path_grow_recv(clrrt_xchg* x, int64_t rows) {
+  if (rows * x->world <= x->p_recv_rows) return CLRRT_OK;
+  const int64_t cap = std::max<int64_t>(rows * x->world, 2 * x->p_recv_rows);
+  if (x->p_recv) XHIP(hipFree(x->p_recv));  // (waits for the last completion's kernel)
+  x->p_recv = nullptr;
+  x->p_recv_rows = 0;
+  XHIP(hipMalloc((void**)&x->p_recv, (size_t)cap * PROW));
+  x->p_recv_rows = cap;
+  return CLRRT_OK;
+}
+
+// The first rank whose agreement record differs from rank 0's (-1: none), and the error every rank then returns.
+int path_disagreement(const clrrt_xchg* x, const PathHdr* all) {
+  for (int r = 1; r < x->world; r++)
+    if (all[r].n != all[0].n || all[r].rows != all[0].rows || all[r].hash != all[0].hash) return r;
+  return -1;
+}
+int path_estate(const clrrt_xchg* x, const PathHdr* all, int r) {
+  return fail(CLRRT_ESTATE, "clrrt_xchg_path_rows: the committed path of rank " + std::to_string(r) + " (" +
+                                std::to_string((long long)all[r].n) + " nodes, " +
+                                std::to_string((long long)all[r].rows) + " rows) differs from rank 0's (" +
+                                std::to_string((long long)all[0].n) + " nodes, " +
+                                std::to_string((long long)all[0].rows) + " rows" +
+                                (all[r].n == all[0].n && all[r].rows == all[0].rows ? ", other headers" : "") +
+                                "): no rows were moved (seen by rank " + std::to_string(x->rank) + ")");
+}
+
+int path_select(clrrt_xchg* x, const PathView& v, hipStream_t st) {
+  PathSelectArgs a{};
+  a.parts = (const uint4*)x->p_recv;
+  a.dst = (uint4*)v.d_rows;
+  a.nodes = v.d_nodes;
+  a.rows = v.rows;
+  a.n = v.n;
+  a.W = x->world;
+  a.self = x->rank;
+  XHIP(launch_path_select(st, a));
+  return CLRRT_OK;
+}
+
+int path_rccl(clrrt_xchg* x, const PathView& v, const PathHdr& mine, hipStream_t st) {
+  // the agreement records travel through the device (RCCL is the only transport between the processes): a second
+  // host wait, before which no row collective is queued
+  x->h_phdr[0] = mine;
+  XHIP(hipMemcpyAsync(x->d_phdr, x->h_phdr, sizeof(PathHdr), hipMemcpyHostToDevice, st));
+  XNCCL(ncclAllGather(x->d_phdr, x->d_phdr + 1, sizeof(PathHdr), ncclChar, x->comm, st));
+  XHIP(hipMemcpyAsync(x->h_phdr + 1, x->d_phdr + 1, sizeof(PathHdr) * x->world, hipMemcpyDeviceToHost, st));
+  XHIP(hipEventRecord(x->ev_sum, st));
+  XHIP(hipEventSynchronize(x->ev_sum));
+  x->pst[1]++;
+  const int bad = path_disagreement(x, x->h_phdr + 1);
+  if (bad >= 0) return path_estate(x, x->h_phdr + 1, bad);
+  if (v.rows == 0) return CLRRT_OK;
+  int rc = path_grow_recv(x, v.rows);
+  if (rc != CLRRT_OK) return rc;
+  XNCCL(ncclAllGather(v.d_rows, x->p_recv, (size_t)v.rows * PROW, ncclChar, x->comm, st));
+  x->pst[1]++;
+  x->pst[2] += v.rows * x->world;
+  return path_select(x, v, st);
+}
+
+int path_local(clrrt_xchg* x, const PathView& v, const PathHdr& mine, hipStream_t st) {
+  clrrt_xchg_group* g = x->group;
+  const int W = x->world;
+  LocalSlot& me = g->slot[x->rank];
+  me.path = mine;
+  me.path_rows = (const char*)v.d_rows;
+  if (hipEventRecord(x->ev_sent, st) != hipSuccess) {
+    g->rv.abandon();
+    return fail(CLRRT_EHIP, "clrrt_xchg_path_rows: hipEventRecord failed");
+  }
+  if (!g->rv.meet())
+    return fail(CLRRT_EHIP, "clrrt_xchg_path_rows: a peer did not reach the path completion within the group's deadline");
+  x->pst[1]++;
+  PathHdr all[MAXW];
+  for (int q = 0; q < W; q++) all[q] = g->slot[q].path;
+  const int bad = path_disagreement(x, all);  // every rank reads the same records: the same verdict everywhere
+  int rc = CLRRT_OK;
+  if (bad < 0 && v.moved > 0) {
+    rc = path_grow_recv(x, v.rows);
+    for (int q = 0; q < W && rc == CLRRT_OK; q++) {
+      if (!v.need[q]) continue;  // nothing is pulled from a rank that owns no node of the path
+      const clrrt_xchg* y = g->slot[q].x;
+      auto pull = [&]() -> int {
+        if (!y || !g->slot[q].path_rows) return fail(CLRRT_EINVAL, "clrrt_xchg_path_rows: a peer published no path rows");
+        XHIP(hipStreamWaitEvent(st, y->ev_sent, 0));
+        char* d = x->p_recv + (size_t)q * v.rows * PROW;
+        if (y->device == x->device)
+          XHIP(hipMemcpyAsync(d, g->slot[q].path_rows, (size_t)v.rows * PROW, hipMemcpyDeviceToDevice, st));
+        else
+          XHIP(hipMemcpyPeerAsync(d, x->device, g->slot[q].path_rows, y->device, (size_t)v.rows * PROW, st));
+        return CLRRT_OK;
+      };
+      rc = pull();
+      if (rc == CLRRT_OK) x->pst[2] += v.rows;
+    }
+    if (rc == CLRRT_OK) {
+      x->pst[1]++;
+      rc = path_select(x, v, st);
+    }
+  }
+  if (rc == CLRRT_OK && hipEventRecord(x->ev_pulled, st) != hipSuccess)
+    rc = fail(CLRRT_EHIP, "clrrt_xchg_path_rows: hipEventRecord failed");
+  if (rc != CLRRT_OK) {
+    g->rv.abandon();
+    return rc;
+  }
+  // no owner goes on to change its path (the next query's transform) before every puller's copies are done; the
+  // meeting also keeps the published records in place until every rank has read them
+  if (!g->rv.meet()) return fail(CLRRT_EHIP, "clrrt_xchg_path_rows: a peer left the path completion before its copies were queued");
+  if (bad >= 0) return path_estate(x, all, bad);
+  for (int q = 0; q < W; q++)
+    if (q != x->rank) XHIP(hipStreamWaitEvent(st, g->slot[q].x->ev_pulled, 0));
+  return CLRRT_OK;
+}
+
 }  // namespace
 
 extern "C" {
 
 const char* clrrt_xchg_last_error(void) { return t_err.c_str(); }
+
+int32_t clrrt_xchg_path_rows(void* user, clrrt_ctx* ctx, int64_t* rows_moved) {
+  clrrt_xchg* x = (clrrt_xchg*)user;
+  if (rows_moved) *rows_moved = 0;
+  if (!x || !ctx) return fail(CLRRT_EINVAL, "clrrt_xchg_path_rows: null argument");
+  if (x->ctx != ctx) return fail(CLRRT_EINVAL, "clrrt_xchg_path_rows: the exchange is not attached to this context");
+  if (!x->have_stream)
+    return fail(CLRRT_ESTATE, "clrrt_xchg_path_rows: no exchange has run yet (the context's stream is taken from "
+                              "the expansion's exchanges)");
+  hipStream_t st = x->stream;
+  XHIP(hipSetDevice(x->device));
+  PathView v;
+  void* dn = nullptr;
+  if (clrrt_path_device(ctx, &dn, &v.d_rows, &v.n, &v.rows) != CLRRT_OK)
+    return fail(CLRRT_EINVAL, "clrrt_path_device failed");
+  v.d_nodes = (clrrt_node*)dn;
+  x->pst[0]++;
+  // the n headers, read once: the hash, the rows to take and the ranks they come from
+  if (v.n > x->h_nodes_cap) {
+    const int cap = std::max(v.n, std::max(64, 2 * x->h_nodes_cap));
+    if (x->h_nodes) XHIP(hipHostFree(x->h_nodes));
+    x->h_nodes = nullptr;
+    x->h_nodes_cap = 0;
+    XHIP(hipHostMalloc((void**)&x->h_nodes, sizeof(clrrt_node) * cap, hipHostMallocDefault));
+    x->h_nodes_cap = cap;
+  }
+  auto read_headers = [&]() -> int {
+    if (v.n == 0) return CLRRT_OK;
+    XHIP(hipMemcpyAsync(x->h_nodes, v.d_nodes, sizeof(clrrt_node) * v.n, hipMemcpyDeviceToHost, st));
+    XHIP(hipEventRecord(x->ev_sum, st));
+    XHIP(hipEventSynchronize(x->ev_sum));  // the completion's host wait
+    return CLRRT_OK;
+  };
+  int rc = read_headers();
+  if (rc != CLRRT_OK) {
+    if (x->group) x->group->rv.abandon();
+    return rc;
+  }
+  for (int i = 0; i < v.n; i++) {
+    const clrrt_node& h = x->h_nodes[i];
+    if (h.owner == x->rank || h.owner < 0 || h.owner >= x->world || h.nrows < 1) continue;
+    v.moved += h.nrows;
+    v.need[h.owner] = true;
+  }
+  PathHdr mine{};
+  mine.n = v.n;
+  mine.rows = v.rows;
+  mine.hash = path_hash(x->h_nodes, v.n);
+  rc = x->group ? path_local(x, v, mine, st) : path_rccl(x, v, mine, st);
+  if (rc != CLRRT_OK) return rc;
+  x->pst[3] += v.moved;
+  if (rows_moved) *rows_moved = v.moved;
+  return CLRRT_OK;
+}
+
+int clrrt_xchg_path_stats(clrrt_xchg* x, int64_t out[4]) {
+  if (!x || !out) return fail(CLRRT_EINVAL, "clrrt_xchg_path_stats: null argument");
+  memcpy(out, x->pst, sizeof(x->pst));
+  return CLRRT_OK;
+}
 
 int clrrt_xchg_unique_id(void* out) {
   static_assert(sizeof(ncclUniqueId) == CLRRT_XCHG_UID_BYTES, "the unique id is 128 bytes");
@@ -414,6 +698,8 @@ int32_t clrrt_xchg_hook(void* user, clrrt_exchange_io* io) {
     return fail(CLRRT_ECAPACITY, "clrrt_xchg_hook: n_local outside the send buffer");
   hipStream_t st = (hipStream_t)io->stream;
   const bool closing = (io->flags & 1) != 0;
+  x->stream = st;  // the path completion queues its work here
+  x->have_stream = true;
   x->st[0]++;
   x->st[3] += closing;
   x->st[4] += io->n_local;
@@ -433,6 +719,7 @@ int clrrt_xchg_attach(clrrt_xchg* x, clrrt_ctx* ctx) {
   if (!x || !ctx) return fail(CLRRT_EINVAL, "clrrt_xchg_attach: null argument");
   const int rc = clrrt_set_shards(ctx, x->rank, x->world, x->send + ROW, (int32_t)x->cap, clrrt_xchg_hook, x);
   if (rc != CLRRT_OK) return fail(rc, std::string("clrrt_set_shards: ") + clrrt_last_error(ctx));
+  x->ctx = ctx;
   return CLRRT_OK;
 }
 
@@ -452,10 +739,11 @@ void clrrt_xchg_destroy(clrrt_xchg* x) {
     if (x->group->slot[x->rank].x == x) x->group->slot[x->rank].x = nullptr;
   }
   if (x->comm) (void)ncclCommDestroy(x->comm);
-  for (void* p : {(void*)x->send, (void*)x->recv, (void*)x->recv_ex, (void*)x->out, (void*)x->d_sum})
+  for (void* p : {(void*)x->send, (void*)x->recv, (void*)x->recv_ex, (void*)x->out, (void*)x->d_sum, (void*)x->p_recv,
+                  (void*)x->d_phdr})
     if (p) (void)hipFree(p);
-  if (x->h_sum) (void)hipHostFree(x->h_sum);
-  if (x->h_hdr) (void)hipHostFree(x->h_hdr);
+  for (void* p : {(void*)x->h_sum, (void*)x->h_hdr, (void*)x->h_nodes, (void*)x->h_phdr})
+    if (p) (void)hipHostFree(p);
   for (hipEvent_t e : {x->ev_sum, x->ev_sent, x->ev_pulled})
     if (e) (void)hipEventDestroy(e);
   delete x;
@@ -530,6 +818,73 @@ int clrrt_xchg_selftest_concat(int32_t device, int32_t W, int32_t bound, const i
   summary[3] = hs.aux_sum;
   memcpy(&summary[4], hs.bbox, 32);
   for (int r = 0; r < W; r++) summary[8 + r] = hs.counts[r];
+  return CLRRT_OK;
+}
+
+int clrrt_xchg_selftest_path_select(int32_t device, int32_t W, int32_t self, int32_t n, const int32_t* owners,
+                                    const int32_t* nrows, void* out_rows, int64_t* out_moved) {
+  if (W < 1 || W > MAXW || self < 0 || self >= W || device < 0 || n < 0 || !out_moved || (n > 0 && (!owners || !nrows)))
+    return fail(CLRRT_EINVAL, "clrrt_xchg_selftest_path_select: bad argument");
+  std::vector<clrrt_node> hn((size_t)n);
+  int64_t R = 0, moved = 0;
+  for (int i = 0; i < n; i++) {
+    if (owners[i] < 0 || owners[i] >= W || nrows[i] < 1)
+      return fail(CLRRT_EINVAL, "clrrt_xchg_selftest_path_select: an owner outside [0, W) or a node without rows");
+    memset(&hn[i], 0, sizeof(clrrt_node));
+    hn[i].nrows = nrows[i];
+    hn[i].owner = owners[i];
+    hn[i].row_offset = R;
+    R += nrows[i];
+    if (owners[i] != self) moved += nrows[i];
+  }
+  *out_moved = 0;
+  if (R > 0 && !out_rows) return fail(CLRRT_EINVAL, "clrrt_xchg_selftest_path_select: null out_rows");
+  std::vector<uint64_t> hp((size_t)W * R * 10);
+  for (int r = 0; r < W; r++)
+    for (int64_t j = 0; j < R; j++)
+      for (int c = 0; c < 10; c++) {
+        const uint64_t b = ((uint64_t)(r + 1) << 44) | ((uint64_t)j << 8) | (uint64_t)c;
+        uint64_t v = b;
+        switch ((j + c) % 5) {
+          case 1: v = 0x7FF8000000000000ull | b; break;
+          case 2: v = 0xFFF0000000000000ull | b; break;
+          case 3: v = 0x8000000000000000ull; break;
+          case 4: v = 0x4000000000000000ull | b; break;
+          default: break;
+        }
+        hp[((size_t)r * R + j) * 10 + c] = v;
+      }
+  XHIP(hipSetDevice(device));
+  char *dp = nullptr, *dd = nullptr;
+  clrrt_node* dn = nullptr;
+  auto run = [&]() -> int {
+    const size_t part = (size_t)R * PROW;
+    XHIP(hipMalloc((void**)&dp, std::max<size_t>(part * W, 16)));
+    XHIP(hipMalloc((void**)&dd, std::max<size_t>(part, 16)));
+    XHIP(hipMalloc((void**)&dn, std::max<size_t>(sizeof(clrrt_node) * n, 16)));
+    if (R > 0) {
+      XHIP(hipMemcpy(dp, hp.data(), part * W, hipMemcpyHostToDevice));
+      XHIP(hipMemcpy(dd, hp.data() + (size_t)self * R * 10, part, hipMemcpyHostToDevice));  // its own pattern
+      XHIP(hipMemcpy(dn, hn.data(), sizeof(clrrt_node) * n, hipMemcpyHostToDevice));
+    }
+    PathSelectArgs a{};
+    a.parts = (const uint4*)dp;
+    a.dst = (uint4*)dd;
+    a.nodes = dn;
+    a.rows = R;
+    a.n = n;
+    a.W = W;
+    a.self = self;
+    XHIP(launch_path_select(nullptr, a));
+    XHIP(hipDeviceSynchronize());
+    if (R > 0) XHIP(hipMemcpy(out_rows, dd, part, hipMemcpyDeviceToHost));
+    return CLRRT_OK;
+  };
+  const int rc = run();
+  for (void* p : {(void*)dp, (void*)dd, (void*)dn})
+    if (p) (void)hipFree(p);
+  if (rc != CLRRT_OK) return rc;
+  *out_moved = moved;
   return CLRRT_OK;
 }
 

@@ -272,9 +272,14 @@ int clrrt_extract_best_path(clrrt_ctx* ctx, int32_t* path, int32_t cap, int32_t*
  *   clrrt_extract_best_path + clrrt_path_commit                     bestNodes = extractBestPath (:51)
  *   clrrt_path_transform(ctx, CLRRT_CAR_TO_WORLD, worldState)      transformNodesCarToworld (:54)  */
 /* bestNodes = the tree nodes ids[0 .. n) (headers and trajectories copied; rows of nodes owned by
- * another rank are zero-filled and counted in *n_remote -- fetch them from the owner and
- * clrrt_path_load the result). */
+ * another rank are zero-filled and counted in *n_remote -- the exchange's path completion,
+ * clrrt_xchg_path_rows of include/clrrt_xchg.h, then takes them from their owners on the device, a
+ * collective that every rank calls after its commit and before clrrt_path_transform). */
 int clrrt_path_commit(clrrt_ctx* ctx, const int32_t* ids, int32_t n, int32_t* n_remote);
+/* Engine extension: device addresses of the committed path (n headers with path-local row_offset, n_rows rows of 10
+ * doubles), valid until the next call that changes the path.  Work queued on the context's stream is ordered with the
+ * engine's own. */
+int clrrt_path_device(clrrt_ctx* ctx, void** dev_nodes, double** dev_rows, int32_t* n, int64_t* n_rows);
 /* Replace the committed path with host data: n headers whose row_offset/nrows index `rows`
  * (n_rows rows of 10 doubles); every node needs nrows >= 1. */
 int clrrt_path_load(clrrt_ctx* ctx, const clrrt_node* nodes, int32_t n, const double* rows, int64_t n_rows);

@@ -726,6 +726,8 @@ struct PlanReport {
   std::vector<int32_t> path;    /* bestNodes as tree ids, root -> goal */
   float best_cost = 0;
   int64_t counters[4] = {0, 0, 0, 0};  /* sim_count, fail_collision, fail_acclimit, fail_iterlimit (:9, :45) */
+  int64_t rows_fetched = 0;     /* rows the path completer took from other ranks (0 without one) */
+  int64_t deferred = 0;         /* clrrt_stats::deferred of the expansion (option "defer_steps"; per rank when sharded) */
 };
 
 class MotionPlanner {
@@ -751,6 +753,21 @@ class MotionPlanner {
 
   clrrt_ctx* ctx() { return ctx_; }
   clrrt_rng& rng() { return rng_; }
+
+  /* Sharded queries (clrrt_set_shards with world > 1; one MotionPlanner per rank, every rank given the same seed,
+   * state, detections and requests).  The host attaches its exchange to ctx() itself -- with libclrrt_xchg:
+   * clrrt_xchg_attach(x, mp.ctx()) -- and names the collective that completes the committed path's rows across the
+   * ranks, since a node's trajectory stays on the rank that grew it: setPathCompleter(clrrt_xchg_path_rows, x) (the
+   * signature is that function's; this header depends on clrrt.h only).  planMotion then calls it in EVERY query,
+   * right after clrrt_path_commit -- also with an empty path or no foreign node, because the call is collective --
+   * and a non-zero return throws.  Without a completer a commit that leaves rows on other ranks throws instead of
+   * passing a path with zeroed segments on (to the world-frame transform, the MPC message and the next query's
+   * initializeTree).  Config::batch is the GLOBAL number of samples per round, cap.max_batch this rank's slice.
+   * draw_tree is not supported under sharding: the markers of nodes other ranks own have zeroed rows. */
+  void setPathCompleter(int32_t (*fn)(void* user, clrrt_ctx*, int64_t* rows_moved), void* user) {
+    completer_ = fn;
+    completer_user_ = user;
+  }
 
   /* updateState (motionplanner.cpp:89-94): state = [x, y, theta, delta, v, a] in the world frame */
   void updateState(const std::vector<double>& s) {
@@ -805,8 +822,18 @@ class MotionPlanner {
     ids.resize(n_path);
     int32_t n_remote = 0;
     check(ctx_, clrrt_path_commit(ctx_, ids.data(), n_path, &n_remote), "clrrt_path_commit");
+    int64_t rows_fetched = 0;
+    if (completer_) {  // collective: every query, whatever the path holds
+      const int32_t crc = completer_(completer_user_, ctx_, &rows_fetched);
+      if (crc != 0) throw Error("planMotion: the path completer -> " + std::to_string(crc));
+    } else if (n_remote > 0) {
+      throw Error("planMotion: " + std::to_string(n_remote) + " node(s) of the committed path have their rows on "
+                  "other ranks and no path completer is set (setPathCompleter)");
+    }
     check(ctx_, clrrt_path_transform(ctx_, CLRRT_CAR_TO_WORLD, world), "clrrt_path_transform");  // :54
     if (rep) {
+      rep->rows_fetched = rows_fetched;
+      rep->deferred = st.deferred;
       rep->reinit_outcome = oc;
       rep->iterations = st.iterations;
       rep->tree_size = n_nodes;
@@ -859,6 +886,8 @@ class MotionPlanner {
   clrrt_rng rng_;
   std::vector<double> state_;
   std::vector<clrrt_obstacle> det_;
+  int32_t (*completer_)(void*, clrrt_ctx*, int64_t*) = nullptr;
+  void* completer_user_ = nullptr;
 };
 
 }  // namespace clrrt_adapter

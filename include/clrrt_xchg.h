@@ -32,7 +32,7 @@
  *               (clrrt_expand then returns CLRRT_EHIP) within timeout_ms.
  *
  * All entry points return an int status: 0 ok, CLRRT_EINVAL (-1), CLRRT_EHIP (-2: a HIP or RCCL call failed, or the
- * rendezvous timed out), CLRRT_ECAPACITY (-3); clrrt_xchg_last_error gives the message of the calling thread's last
+ * rendezvous timed out), CLRRT_ECAPACITY (-3), CLRRT_ESTATE (-4: the ranks' committed paths differ); clrrt_xchg_last_error gives the message of the calling thread's last
  * failure.  An exchange object belongs to one host thread at a time (its rank's), like a clrrt_ctx.
  */
 #ifndef CLRRT_XCHG_H
@@ -88,6 +88,34 @@ void* clrrt_xchg_records(clrrt_xchg* x);
 int clrrt_xchg_stats(clrrt_xchg* x, int64_t out[8]);
 void clrrt_xchg_destroy(clrrt_xchg* x);
 
+/* ---- the committed path's rows across ranks (a sharded planMotion: 5 Hz replanning from the committed path) ----
+ * In a sharded expansion a node's trajectory rows stay on the rank that grew it (clrrt_node::owner), so
+ * clrrt_path_commit leaves the rows of foreign nodes zero-filled.  Every rank commits the same node ids (the headers
+ * are replicated), so the paths have the same n and the same path-local row layout; but the ranks do NOT agree on
+ * `owner` for every node: a node kept by clrrt_tree_init_from_path is stamped with the local rank on every rank (each
+ * holds its own copy of those rows), only a node grown in a sharded round has one owner for all.  So every rank offers
+ * its whole path row buffer (R rows, zeros where foreign) and the receiver picks per node by ITS OWN view of owner:
+ *   1. agreement: the host reads the n headers once -- the completion's host wait -- and hashes their first 148
+ *      bytes; (n, R, hash) of every rank is gathered and compared on the host (in-process through the rendezvous;
+ *      RCCL by a 32-byte all-gather, whose read is a second wait there).  If a rank differs, every rank returns
+ *      CLRRT_ESTATE (the message names the first rank that differs from rank 0) and no row collective is started, so
+ *      a collective with unequal counts cannot happen.  n = 0 everywhere: ok, 0 rows.
+ *   2. rows: RCCL -- one ncclAllGather of R x 80 bytes on the engine's stream; in-process -- the ranks publish their
+ *      row pointer and an event, meet, and each pulls the buffers of the ranks that own a node it needs (no others);
+ *      a second meeting keeps an owner from changing its path before the pullers' copies are done.
+ *   3. selection: k_xchg_path_select copies, for every node whose owner is another rank, that rank's rows into the
+ *      context's path rows (clrrt_path_device) as raw bits (the sign of zero and NaN payloads survive).
+ * All of it is queued on the context's stream (the one the attached context's last exchange ran on).
+ * A rank that fails between its expansion and the completion leaves its peers in the completion: the in-process
+ * transport bounds that wait by the group's deadline (CLRRT_EHIP); RCCL cannot bound it (the collective waits for the
+ * missing rank), so an RCCL host that abandons a query must tear its communicator down.
+ *
+ * Collective over the exchange's ranks, after clrrt_path_commit on every rank and before clrrt_path_transform: every
+ * path node whose rows this rank does not own takes them from its owner.  user = the clrrt_xchg object (the
+ * signature is the adapter's path-completer hook).  *rows_moved: rows this rank received into its path. */
+int32_t clrrt_xchg_path_rows(void* user, clrrt_ctx* ctx, int64_t* rows_moved);
+int clrrt_xchg_path_stats(clrrt_xchg* x, int64_t out[4]); /* completions, collectives, rows gathered, rows taken */
+
 /* Test hook: k_xchg_concat on `device` over patterned parts.  W parts of (bound + 1) rows (row 0 a header with
  * counts[r], elapsed[r], aux[r], bbox[4 r .. 4 r + 4)) and, with excess_rows > 0, W excess parts of excess_rows rows
  * (rows bound .. of each rank).  Row j of rank r is filled with the bytes (uint8)(r * 131 + j * 7 + b * 3 + 1) for
@@ -98,6 +126,18 @@ void clrrt_xchg_destroy(clrrt_xchg* x);
 int clrrt_xchg_selftest_concat(int32_t device, int32_t W, int32_t bound, const int32_t* counts, const double* elapsed,
                                const int64_t* aux, const double* bbox, int32_t excess_rows, void* out_rows,
                                int64_t out_cap, int64_t* summary);
+
+/* Test hook: k_xchg_path_select on `device` as rank `self` of W over a path of n nodes (owners[i] in [0, W),
+ * nrows[i] >= 1; row offsets are the prefix sums of nrows, R their total) and W patterned parts of R rows.  Entry
+ * (row j, column c) of rank r's part is the raw 64-bit pattern, with b = (r + 1) << 44 | j << 8 | c and k = (j + c) % 5:
+ *   k = 0: b (a subnormal)         k = 1: 0x7FF8000000000000 | b (a quiet NaN with payload b)
+ *   k = 2: 0xFFF0000000000000 | b (a negative signalling NaN, payload b)
+ *   k = 3: 0x8000000000000000 (-0.0)         k = 4: 0x4000000000000000 | b (a finite number)
+ * The rank's own rows are pre-filled with its own pattern (r = self).  Writes the R rows after the selection to
+ * out_rows (R x 10 doubles) and the rows taken from other ranks to *out_moved.  CLRRT_EINVAL for W outside [1, 64],
+ * self outside [0, W), n < 0, an owner outside [0, W) or nrows[i] < 1. */
+int clrrt_xchg_selftest_path_select(int32_t device, int32_t W, int32_t self, int32_t n, const int32_t* owners,
+                                    const int32_t* nrows, void* out_rows, int64_t* out_moved);
 
 #ifdef __cplusplus
 }

@@ -16,7 +16,7 @@ import os
 import numpy as np
 
 from . import abi
-from .abi import (CLRRT_COLLISION_OBB, CLRRT_COLLISION_STUB, CLRRT_MODE_BATCH,  # noqa: F401
+from .abi import (CLRRT_COLLISION_OBB, CLRRT_COLLISION_OCC, CLRRT_COLLISION_STUB, CLRRT_MODE_BATCH,  # noqa: F401
                   CLRRT_MODE_EXACT, ROLL_NAMES)
 
 PKG_DIR = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -40,6 +40,8 @@ _SIGS = {
     "clrrt_set_stream": (C.c_int, [C.c_void_p, C.c_void_p]),
     "clrrt_set_params": (C.c_int, [C.c_void_p, P(abi.Params)]),
     "clrrt_set_obstacles": (C.c_int, [C.c_void_p, P(abi.Obstacle), C.c_int32]),
+    "clrrt_set_occupancy": (C.c_int, [C.c_void_p, P(abi.Occupancy), C.c_void_p]),
+    "clrrt_occupancy_info": (C.c_int, [C.c_void_p, P(abi.OccupancyInfo)]),
     "clrrt_set_rank": (C.c_int, [C.c_void_p, C.c_int32]),
     "clrrt_set_shards": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, EXCHANGE_FN, C.c_void_p]),
     "clrrt_tree_init": (C.c_int, [C.c_void_p, P(C.c_double)]),
@@ -242,6 +244,25 @@ class Planner:
         arr = (abi.Obstacle * max(1, len(obs)))()
         C.memmove(arr, obs.ctypes.data, obs.nbytes)
         self._chk(self.L.clrrt_set_obstacles(self.h, arr, len(obs)), "set_obstacles")
+
+    def set_occupancy(self, x0=0.0, y0=0.0, res=1.0, cells2d=None, inflate=None):
+        """The static occupancy grid of CLRRT_COLLISION_OCC (clrrt_set_occupancy): cells2d[j, i] != 0 marks the cell
+        whose centre is (x0 + (i + 0.5) res, y0 + (j + 0.5) res), car frame.  inflate None: res sqrt(2) / 2, the
+        cell's half diagonal (a box that touches any part of an occupied cell then hits).  cells2d None clears."""
+        if cells2d is None:
+            self._chk(self.L.clrrt_set_occupancy(self.h, None, None), "set_occupancy")
+            return
+        cells = np.ascontiguousarray(np.asarray(cells2d) != 0, dtype=np.uint8)
+        if cells.ndim != 2:
+            raise ValueError("cells2d must be a 2D array [h, w]")
+        inflate = res * np.sqrt(2.0) / 2.0 if inflate is None else inflate
+        o = abi.Occupancy(x0, y0, res, inflate, cells.shape[1], cells.shape[0])
+        self._chk(self.L.clrrt_set_occupancy(self.h, C.byref(o), C.c_void_p(cells.ctypes.data)), "set_occupancy")
+
+    def occupancy_info(self):
+        o = abi.OccupancyInfo()
+        self._chk(self.L.clrrt_occupancy_info(self.h, C.byref(o)), "occupancy_info")
+        return {k: getattr(o, k) for k, _ in abi.OccupancyInfo._fields_}
 
     def tree_init(self, root=None):
         root = np.zeros(10) if root is None else np.ascontiguousarray(root, dtype=np.float64)

@@ -15,6 +15,8 @@ CLRRT_PARENT_PREV = -2  # goal-biased record: parent = the record before it (inc
 CLRRT_MODE_BATCH = 1
 CLRRT_COLLISION_STUB = 0
 CLRRT_COLLISION_OBB = 1
+CLRRT_COLLISION_OCC = 2  # the static occupancy grid (clrrt_set_occupancy), then the OBB test
+OCC_NONE, OCC_LDS, OCC_GLOBAL = 0, 1, 2  # CLRRT_OCC_*: where the rollout kernels hold the grid's bitmaps
 
 ROLL_ITERLIMIT, ROLL_END, ROLL_GOAL, ROLL_COLLISION, ROLL_ACCLIMIT = range(5)
 ROLL_NAMES = {ROLL_ITERLIMIT: "iterlimit", ROLL_END: "end", ROLL_GOAL: "goal",
@@ -46,6 +48,17 @@ class Params(C.Structure):
 
 class Obstacle(C.Structure):
     _fields_ = [(n, C.c_double) for n in ("cx", "cy", "theta", "size_x", "size_y", "vx", "vy")]
+
+
+class Occupancy(C.Structure):  # clrrt_occupancy
+    _fields_ = [("x0", C.c_double), ("y0", C.c_double), ("res", C.c_double), ("inflate", C.c_double),
+                ("w", C.c_int32), ("h", C.c_int32)]
+
+
+class OccupancyInfo(C.Structure):  # clrrt_occupancy_info_t
+    _fields_ = [("w", C.c_int32), ("h", C.c_int32), ("reach_w", C.c_int32), ("reach_h", C.c_int32),
+                ("reach_k", C.c_int32), ("placement", C.c_int32), ("occupied", C.c_int64),
+                ("map_bytes", C.c_int64), ("bake_ms", C.c_double)]
 
 
 class Node(C.Structure):
@@ -115,6 +128,7 @@ def _check_sizes():
     assert C.sizeof(Sample) == 24
     assert C.sizeof(RolloutResult) == 136, C.sizeof(RolloutResult)
     assert C.sizeof(ExchangeIO) == 128, C.sizeof(ExchangeIO)
+    assert C.sizeof(Occupancy) == 40 and C.sizeof(OccupancyInfo) == 48
 
 
 _check_sizes()

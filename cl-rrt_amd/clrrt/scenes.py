@@ -41,3 +41,24 @@ def urban_scene(n_static, n_moving=0, seed=12345):
         vy = g.u(-2.0, 2.0)
         out.append((x, y, th, sx, sy, vx, vy))
     return np.asarray(out, dtype=np.float64).reshape(-1, 7)
+
+
+def rasterize(obstacles, x0, y0, res, w, h):
+    """Occupancy cells (uint8 [h, w]) of the static obstacles' boxes: cell (i, j) is set when its centre
+    (x0 + (i + 0.5) res, y0 + (j + 0.5) res) lies inside a box with zero velocity (the box of an obstacle:
+    centre cx, cy, heading theta, size_y along the heading and size_x across it, each halved twice as
+    getOBBvector does -- old_collisioncheck.cpp:6-22).  Moving obstacles are left out: they stay boxes."""
+    obs = np.asarray(obstacles, dtype=np.float64).reshape(-1, 7)
+    cx = x0 + (np.arange(w) + 0.5) * res
+    cy = y0 + (np.arange(h) + 0.5) * res
+    X, Y = np.meshgrid(cx, cy)
+    out = np.zeros((h, w), dtype=bool)
+    for ox, oy, th, sx, sy, vx, vy in obs:
+        if vx != 0.0 or vy != 0.0:
+            continue
+        c, s = np.cos(th), np.sin(th)
+        dx, dy = X - ox, Y - oy
+        u = dx * c + dy * s
+        v = dy * c - dx * s
+        out |= (np.abs(u) <= sy / 4.0) & (np.abs(v) <= sx / 4.0)
+    return out.astype(np.uint8)

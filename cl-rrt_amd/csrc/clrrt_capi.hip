@@ -65,6 +65,14 @@ struct clrrt_ctx {
   void* grid_buf = nullptr;    // start | items | mov
   size_t grid_bytes = 0;
   int grid_exempt = 0;         // obstacles exempt from culling (always-tested list, see build_grid)
+  // the static occupancy grid (CLRRT_COLLISION_OCC, clrrt_set_occupancy): the baked maps' device view (w == 0:
+  // none), their buffer (cell bytes | count | occ words | reach words), the occupied count and the bake's events
+  OccGrid occ{};
+  void* occ_buf = nullptr;
+  size_t occ_bytes = 0;
+  int64_t occ_count = 0;
+  hipEvent_t occ_ev[2] = {nullptr, nullptr};
+  float occ_bake_ms = 0.f;
   // round buffers (capacity cap.max_batch samples)
   clrrt_sample* d_samples = nullptr;
   float* pk = nullptr;
@@ -400,6 +408,7 @@ struct clrrt_ctx {
 // ------------------------------------------------------------------------------------------ util
 static void pf_reset(clrrt_ctx* c);
 static int flush_replays(clrrt_ctx* c);
+static RollArgs roll_args(clrrt_ctx* c, int njobs);
 static int append_nodes(clrrt_ctx* c, const clrrt_node* dev_nodes, int n);
 static int watchdog_check(clrrt_ctx* c);
 static void defer_roll_args(clrrt_ctx* c, RollArgs& a, bool capped);
@@ -467,6 +476,11 @@ static void drain_timers(clrrt_ctx* c) {
   c->ev_pending.clear();
 }
 
+// The grid the kernels test: the baked one under CLRRT_COLLISION_OCC, none otherwise.
+static OccGrid occ_view(const clrrt_ctx* c) {
+  return c->params.collision_mode == CLRRT_COLLISION_OCC ? c->occ : OccGrid{};
+}
+
 // ------------------------------------------------------------------------------------------ params
 static void derive(const clrrt_params& q, DevParams& d, int n_obs) {
   memset(&d, 0, sizeof(d));
@@ -495,13 +509,14 @@ static void derive(const clrrt_params& q, DevParams& d, int n_obs) {
   d.gbLx = g[0] + R1 * cos(g[2] - M_PI_2); d.gbLy = g[1] + R1 * cos(g[2] - M_PI_2);
   d.gbRx = g[0] + R1 * cos(g[2] + M_PI_2); d.gbRy = g[1] + R1 * cos(g[2] + M_PI_2);
   d.bend = q.bend; d.obs_use_pred = q.obs_use_pred; d.sort_limit = std::min(q.sort_limit, CAND_K);
-  d.coll_mode = q.collision_mode;
+  // CLRRT_COLLISION_OCC: the kernels' obstacle-list code is mode 1's; the grid test is the OCC instantiations'
+  d.coll_mode = q.collision_mode == CLRRT_COLLISION_OCC ? CLRRT_COLLISION_OBB : q.collision_mode;
   int n = 0;
   while (n < (20 / q.sim_dt)) n++;  // `for(int i = 0; i<(20/sim_dt); i++)` simulation.cpp:58
   d.n_steps_max = n;
   d.use_exp = !(q.Wcost[2] == 0.0 && q.Wcost[3] >= 0.0);  // W2*exp(-W3*Dobs) is exactly +0 otherwise
   d.n_obs = n_obs;
-  d.need_gap = (q.collision_mode == CLRRT_COLLISION_OBB) && d.use_exp;
+  d.need_gap = (d.coll_mode == CLRRT_COLLISION_OBB) && d.use_exp;
 }
 
 
@@ -627,7 +642,7 @@ static void free_all(clrrt_ctx* c) {
   if (c->side) hipStreamSynchronize(c->side);  // side-stream work (prefetched search) uses the *2 buffers
   void* ptrs[] = {c->tree, c->nn, c->arena, c->obs, c->d_samples, c->pk, c->pi, c->cand, c->ckey, c->ncand,
                   c->ctie, c->sort_scratch, c->res_spec, c->regnodes, c->res_gb, c->gbnodes, c->so, c->first_conflict,
-                  c->out_nodes, c->jobs, c->slots, c->rep_buf, c->totals, c->work_ctr, c->grid_buf,
+                  c->out_nodes, c->jobs, c->slots, c->rep_buf, c->totals, c->work_ctr, c->grid_buf, c->occ_buf,
                   c->nn_seed, c->d_bbox, c->roll_q, c->roll_best, c->roll_perm, c->roll_pflag,
                   c->goal_recs, c->bp_path, c->path_nodes, c->path_rows, c->ri_int, c->ri_off, c->ri_cost,
                   c->ri_terms, c->nnw.keys, c->nnw.keys2, c->nnw.vals, c->nnw.vals2, c->nnw.tmp, c->nnw.P, c->nnw.Q,
@@ -648,6 +663,8 @@ static void free_all(clrrt_ctx* c) {
                    c->def.carry[1]};
   for (void* p : dptrs)
     if (p) hipFree(p);
+  for (auto e : c->occ_ev)
+    if (e) hipEventDestroy(e);
   if (c->h_samples) hipHostFree(c->h_samples);
   if (c->h_samples2) hipHostFree(c->h_samples2);
   if (c->h_samples3) hipHostFree(c->h_samples3);
@@ -1012,6 +1029,99 @@ int clrrt_set_obstacles(clrrt_ctx* c, const clrrt_obstacle* o, int32_t m) {
   return build_grid(c, b);
 }
 
+int clrrt_set_occupancy(clrrt_ctx* c, const clrrt_occupancy* o, const uint8_t* cells) {
+  if (!c) return CLRRT_EINVAL;
+  HIPC(c, hipSetDevice(c->device));
+  if (!o || o->w == 0) {  // clear
+    const int frc = flush_replays(c);  // pending replays collide against the scene they were committed with
+    if (frc != CLRRT_OK) return frc;
+    c->occ = OccGrid{};
+    c->occ_count = 0;
+    c->occ_bake_ms = 0.f;
+    return CLRRT_OK;
+  }
+  if (o->w < 0 || o->w > 2048) return fail(c, CLRRT_EINVAL, "set_occupancy: w outside [0, 2048]");
+  if (o->h < 1 || o->h > 2048) return fail(c, CLRRT_EINVAL, "set_occupancy: h outside [1, 2048]");
+  if ((int64_t)o->w * o->h > ((int64_t)1 << 22)) return fail(c, CLRRT_EINVAL, "set_occupancy: w * h above 2^22");
+  if (!std::isfinite(o->x0)) return fail(c, CLRRT_EINVAL, "set_occupancy: x0 is not finite");
+  if (!std::isfinite(o->y0)) return fail(c, CLRRT_EINVAL, "set_occupancy: y0 is not finite");
+  if (!(std::isfinite(o->res) && o->res > 0.0)) return fail(c, CLRRT_EINVAL, "set_occupancy: res is not finite and > 0");
+  if (!(std::isfinite(o->inflate) && o->inflate >= 0.0 && o->inflate <= 1000.0))
+    return fail(c, CLRRT_EINVAL, "set_occupancy: inflate is not finite and within [0, 1000]");
+  if (!cells) return fail(c, CLRRT_EINVAL, "set_occupancy: cells is NULL");
+  // the reach map (clrrt_occ.hpp): cells of rk x rk occupancy cells, about max(0.5 m, R / 8) wide, rm of them around
+  // the grid; Rc: the reach radius plus the rounding slack, in occupancy cells
+  const double R = std::sqrt(2.424 * 2.424 + 1.0) + o->inflate * std::sqrt(2.0);
+  const double ext = std::max(o->w, o->h) * o->res + 2.0 * R;
+  const double mag = std::fabs(o->x0) + std::fabs(o->y0) + ext;
+  if (!(o->res >= mag * (1.0 / 1073741824.0)))
+    return fail(c, CLRRT_EINVAL, "set_occupancy: res is below 2^-30 of the grid's coordinates");
+  OccGrid g{};
+  g.x0 = o->x0; g.y0 = o->y0; g.res = o->res; g.inflate = o->inflate;
+  g.w = o->w; g.h = o->h;
+  g.ws = 2 * ((o->w + 63) / 64);
+  g.rk = std::max(1, (int)std::floor(std::max(0.5, R / 8.0) / o->res + 0.5));
+  const double Rc = (R + o->res / 64.0 + 1e-9 * mag) / o->res;
+  g.rm = (int)std::ceil(Rc / g.rk) + 1;
+  g.rw = (o->w + g.rk - 1) / g.rk + 2 * g.rm;
+  g.rh = (o->h + g.rk - 1) / g.rk + 2 * g.rm;
+  g.rws = 2 * ((g.rw + 63) / 64);
+  g.rres = g.rk * o->res;
+  g.rx0 = o->x0 - g.rm * g.rres;
+  g.ry0 = o->y0 - g.rm * g.rres;
+  const size_t ncell = (size_t)o->w * o->h;
+  const size_t cell_b = (ncell + 255) / 256 * 256;
+  const size_t occ_b = sizeof(uint32_t) * (size_t)g.h * g.ws, reach_b = sizeof(uint32_t) * (size_t)g.rh * g.rws;
+  const size_t need = cell_b + 256 + occ_b + reach_b;
+  const int frc = flush_replays(c);  // pending replays collide against the scene they were committed with
+  if (frc != CLRRT_OK) return frc;
+  HIPC(c, hipStreamSynchronize(c->stream));  // (no launch still reads the old maps)
+  if (need > c->occ_bytes) {
+    if (c->occ_buf) HIPC(c, hipFree(c->occ_buf));
+    c->occ_buf = nullptr;
+    c->occ_bytes = 0;
+    c->occ = OccGrid{};
+    HIPC(c, hipMalloc(&c->occ_buf, need));
+    c->occ_bytes = need;
+  }
+  for (auto& e : c->occ_ev)
+    if (!e) HIPC(c, hipEventCreate(&e));
+  uint8_t* d_cells = (uint8_t*)c->occ_buf;
+  unsigned int* d_count = (unsigned int*)(d_cells + cell_b);
+  g.occ = (const uint32_t*)(d_cells + cell_b + 256);
+  g.reach = (const uint32_t*)(d_cells + cell_b + 256 + occ_b);
+  c->occ = OccGrid{};  // (a failure below leaves no grid)
+  unsigned int count = 0;
+  HIPC(c, hipEventRecord(c->occ_ev[0], c->stream));
+  HIPC(c, hipMemcpyAsync(d_cells, cells, ncell, hipMemcpyHostToDevice, c->stream));
+  HIPC(c, hipMemsetAsync(d_count, 0, sizeof(unsigned int), c->stream));
+  HIPC(c, launch_occ_bake(c->stream, d_cells, g, Rc, d_count));
+  HIPC(c, hipEventRecord(c->occ_ev[1], c->stream));
+  HIPC(c, hipMemcpyAsync(&count, d_count, sizeof(count), hipMemcpyDeviceToHost, c->stream));
+  HIPC(c, hipStreamSynchronize(c->stream));
+  HIPC(c, hipEventElapsedTime(&c->occ_bake_ms, c->occ_ev[0], c->occ_ev[1]));
+  c->occ = g;
+  c->occ_count = count;
+  return CLRRT_OK;
+}
+
+int clrrt_occupancy_info(clrrt_ctx* c, clrrt_occupancy_info_t* out) {
+  if (!c || !out) return CLRRT_EINVAL;
+  memset(out, 0, sizeof(*out));
+  const OccGrid& g = c->occ;
+  if (g.w <= 0) return CLRRT_OK;
+  out->w = g.w; out->h = g.h;
+  out->reach_w = g.rw; out->reach_h = g.rh; out->reach_k = g.rk;
+  RollArgs a = roll_args(c, 0);
+  a.occ = g;  // (the placement a mode-2 launch takes, whichever mode is set now)
+  a.coop_enable = c->roll_coop;
+  out->placement = roll_occ_in_lds(a) ? CLRRT_OCC_LDS : CLRRT_OCC_GLOBAL;
+  out->occupied = c->occ_count;
+  out->map_bytes = (int64_t)occ_map_bytes(g);
+  out->bake_ms = c->occ_bake_ms;
+  return CLRRT_OK;
+}
+
 int clrrt_tree_init(clrrt_ctx* c, const double root_state[10]) {
   if (!c || !root_state) return CLRRT_EINVAL;
   pf_reset(c);
@@ -1313,6 +1423,7 @@ int clrrt_tree_init_from_path(clrrt_ctx* c, const double car_state[6], int32_t* 
     return fail(c, CLRRT_ECAPACITY, "tree_init_from_path: committed path exceeds the tree capacity");
   ReinitArgs a;
   a.p = c->dp;
+  a.occ = occ_view(c);
   a.obs = c->obs;
   a.pn = c->path_nodes;
   a.n = c->path_n;
@@ -1601,6 +1712,7 @@ static RollArgs roll_args(clrrt_ctx* c, int njobs) {
   a.arena = c->arena;
   a.ctr = c->work_ctr;
   a.grid = c->grid;
+  a.occ = occ_view(c);
   a.njobs = njobs;
   return a;
 }
@@ -3660,7 +3772,8 @@ int clrrt_obstacle_distance(clrrt_ctx* c, const double* states, int32_t n, doubl
   hipError_t e = hipMalloc((void**)&din, sizeof(double) * 10 * (size_t)n);
   if (e == hipSuccess) e = hipMalloc((void**)&dout, sizeof(double) * (size_t)n);
   if (e == hipSuccess) e = hipMemcpyAsync(din, states, sizeof(double) * 10 * (size_t)n, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = launch_obs_distance(c->stream, c->dp, c->obs, din, n, dout);
+  const OccGrid og = occ_view(c);
+  if (e == hipSuccess) e = launch_obs_distance(c->stream, c->dp, c->obs, din, n, dout, &og);
   if (e == hipSuccess) e = hipMemcpyAsync(out, dout, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
   hipFree(din);

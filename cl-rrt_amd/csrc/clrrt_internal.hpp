@@ -91,6 +91,20 @@ struct ObsGrid {
   float x0, y0, inv;
 };
 
+// The static occupancy grid of CLRRT_COLLISION_OCC as the kernels see it (baked by clrrt_set_occupancy, see
+// clrrt_occ.hpp): the bit-packed occupancy map (cell (i, j): bit i & 31 of occ[j ws + (i >> 5)]) and the reach map
+// (rw x rh cells of rk x rk occupancy cells each, rm cells of margin around the grid, rows of rws words).  w == 0:
+// no grid (the mode-1 instantiations run).  in_lds / lds_off: set per launch (occ_place).
+struct OccGrid {
+  const uint32_t* occ;
+  const uint32_t* reach;
+  double x0, y0, res, inflate;
+  double rx0, ry0, rres;
+  int w, h, ws;
+  int rw, rh, rws, rk, rm;
+  int in_lds, lds_off;
+};
+
 struct RollArgs {
   DevParams p;
   ObsGrid grid;
@@ -144,6 +158,7 @@ struct RollArgs {
   const clrrt_node* __restrict__ xreg;
   const clrrt_node* __restrict__ xgb;
   int job_stride;
+  OccGrid occ;  // CLRRT_COLLISION_OCC with a grid set (occ.w > 0): the OCC instantiations run
 };
 
 // k_select over B "views": view v < nd is the still unresolved sample view[v] of an earlier round (deferred
@@ -391,7 +406,13 @@ hipError_t launch_bbox(hipStream_t st, const clrrt_node* recs, const int64_t* n_
 hipError_t launch_append(hipStream_t st, const clrrt_node* in, int n, int64_t base, clrrt_node* tree, NnRec* nn);
 hipError_t launch_selftest_math(hipStream_t st, int fn, const double* a, const double* b, int n, double* out);
 hipError_t launch_obs_distance(hipStream_t st, const DevParams& p, const BakedObs* obs, const double* states, int n,
-                               double* out);
+                               double* out, const OccGrid* occ = nullptr);
+// clrrt_set_occupancy's bake: the cell bytes into g.occ, then g.reach from it; Rc = the reach radius in cells
+// (clrrt_occ.hpp), *count += occupied cells.
+hipError_t launch_occ_bake(hipStream_t st, const uint8_t* cells, const OccGrid& g, double Rc, unsigned int* count);
+// Bytes of the two maps, and whether the persistent rollout launch of these arguments holds them in LDS.
+size_t occ_map_bytes(const OccGrid& g);
+bool roll_occ_in_lds(const RollArgs& a);
 // Whether launch_rollout_persistent runs the wave-cooperative collision check (k_roll_run<_, true, _>) for these
 // arguments: option roll_coop, OBB collision without the gap value, a static grid, and LDS room for the scratch.
 bool roll_coop_applies(const RollArgs& a);
@@ -425,6 +446,7 @@ struct ReinitArgs {
   int64_t* out;        // [3] outcome, nodes, rows
   int rank;
   int64_t max_nodes, max_rows;
+  OccGrid occ;         // as RollArgs::occ (read from global memory)
 };
 hipError_t launch_gather_nodes(hipStream_t st, const clrrt_node* tree, const int* ids, int n, clrrt_node* out);
 hipError_t launch_path_transform(hipStream_t st, clrrt_node* nodes, int n, double* rows, int64_t nrows, int to_world,

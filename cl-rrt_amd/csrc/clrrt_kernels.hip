@@ -19,6 +19,7 @@
 
 #include "clrrt_dev.hpp"
 #include "clrrt_internal.hpp"
+#include "clrrt_occ.hpp"
 #include "clrrt_stdsort.hpp"
 
 namespace clrrt {
@@ -1014,12 +1015,23 @@ __device__ __forceinline__ int roll_step_post(Roll& r, const DevParams& p, doubl
   return -1;
 }
 
+// CLRRT_COLLISION_OCC (the OCC instantiations): the static occupancy grid first -- a hit is Dobs = 0 with no box test
+// made or counted -- then the obstacle list as mode 1 has it.
 template <bool NEED_GAP>
-__device__ __forceinline__ int roll_step(Roll& r, const DevParams& p, const ObsView& ov, double& col7,
+__device__ __forceinline__ double obs_distance_occ(const Roll& r, const DevParams& p, const ObsView& ov, OccView& oc,
+                                                   uint32_t& tests) {
+  if (occ_hit(oc, r.x0 + 1.424 * r.c2, r.x1 + 1.424 * r.s2, r.x2, r.c2, r.s2)) return 0.0;
+  return obs_distance<NEED_GAP>(r, p, ov, tests);
+}
+
+template <bool NEED_GAP, bool OCC = false>
+__device__ __forceinline__ int roll_step(Roll& r, const DevParams& p, const ObsView& ov, OccView& oc, double& col7,
                                          double& col8, double& col9, WorkCtr& w, PhaseClk* pc = nullptr) {
   const double d2 = roll_step_pre(r, p, col7, col8, col9, w, pc);
   // collision (simulation.cpp:83-86)
-  const double Dobs = obs_distance<NEED_GAP>(r, p, ov, w.box);
+  double Dobs;
+  if constexpr (OCC) Dobs = obs_distance_occ<NEED_GAP>(r, p, ov, oc, w.box);
+  else Dobs = obs_distance<NEED_GAP>(r, p, ov, w.box);
   if (pc) pc->mark(4);
   return roll_step_post(r, p, Dobs, d2);
 }
@@ -1200,9 +1212,9 @@ __device__ __forceinline__ void finish_rollout(const Roll& r, double c7, double 
 // One whole rollout from parent state `ps` along reference R (ref.v generated from pvb = Vstart).  rows
 // (nullable) receives stateArray: element k of row i at rows[(i * 10 + k) * es].  init (nullable)
 // receives the Simulation state after its constructor (reference end and velocity profile).
-template <bool NEED_GAP>
+template <bool NEED_GAP, bool OCC = false>
 __device__ __forceinline__ void run_rollout_ref(const St10& ps, const RefD& R, double pvb, int gb, const DevParams& p,
-                                                const ObsView& ov, double* __restrict__ rows, int64_t es,
+                                                const ObsView& ov, OccView& oc, double* __restrict__ rows, int64_t es,
                                                 RollRes& out, WorkCtr& w, Roll* init = nullptr,
                                                 PhaseClk* pc = nullptr) {
   Roll r;
@@ -1219,7 +1231,7 @@ __device__ __forceinline__ void run_rollout_ref(const St10& ps, const RefD& R, d
   for (int i = 0; i < p.n_steps_max; i++) {
     steps++;
     if (pc) pc->mark(0);
-    int o = roll_step<NEED_GAP>(r, p, ov, c7, c8, c9, w, pc);
+    int o = roll_step<NEED_GAP, OCC>(r, p, ov, oc, c7, c8, c9, w, pc);
     if (rows) store_row(rows + (int64_t)steps * 10 * es, es, r, c7, c8, c9);
     if (pc) pc->mark(5);
     if (o >= 0) { outcome = o; break; }
@@ -1235,7 +1247,8 @@ __device__ __forceinline__ void run_rollout(const St10& ps, double pbx, double p
                             double sy, const DevParams& p, const ObsView& ov, double* __restrict__ rows,
                             int64_t es, RollRes& out, WorkCtr& w) {
   const RefD R = gb ? make_goal_ref(pbx, pby, p) : make_ref(pbx, pby, sx, sy, p);
-  run_rollout_ref<NEED_GAP>(ps, R, pvb, gb, p, ov, rows, es, out, w);
+  OccView oc{};
+  run_rollout_ref<NEED_GAP>(ps, R, pvb, gb, p, ov, oc, rows, es, out, w);
 }
 
 
@@ -1320,11 +1333,13 @@ __device__ __forceinline__ ObsView stage_obstacles(const RollArgs& a, float4* ld
 #ifndef CLRRT_ROLLOUT_WAVES
 #define CLRRT_ROLLOUT_WAVES 1
 #endif
-template <int SRC, bool NEED_GAP>
+template <int SRC, bool NEED_GAP, bool OCC = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CLRRT_ROLLOUT_WAVES))) k_rollout(RollArgs a) {
   extern __shared__ float4 lds[];
   glibc::stage_tables();
   const ObsView ov = stage_obstacles<NEED_GAP>(a, lds);
+  OccView oc{};
+  if constexpr (OCC) oc = occ_stage(a.occ, lds);
   CLRRT_PARAMS_DECL(P);
   const int gt = blockIdx.x * blockDim.x + threadIdx.x;
   const int js = a.job_stride > 1 ? a.job_stride : 1;
@@ -1355,8 +1370,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CLRRT_
       for (int k = 0; k < 10; k++) ps.v[k] = sj.st[k];
       RollRes out;
       Roll ini;
-      run_rollout_ref<NEED_GAP>(ps, R, sj.vstart, sj.gb, P, ov, sj.row_off >= 0 ? a.arena + sj.row_off * 10 : nullptr,
-                                1, out, w, &ini);
+      run_rollout_ref<NEED_GAP, OCC>(ps, R, sj.vstart, sj.gb, P, ov, oc,
+                                     sj.row_off >= 0 ? a.arena + sj.row_off * 10 : nullptr, 1, out, w, &ini);
       a.res[j] = out;
       if (sj.ref_off >= 0) {  // the reference the Simulation used, with the profile it generated
         double* o = a.refv + sj.ref_off;
@@ -1404,7 +1419,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CLRRT_
     for (int pass = 0; pass < 2; pass++) {
       RollRes out;
       const RefD R = gb ? make_goal_ref(pbx, pby, P) : make_ref(pbx, pby, sx, sy, P);
-      run_rollout_ref<NEED_GAP>(ps, R, pvb, gb, P, ov, rows, es, out, w, nullptr, pc);
+      run_rollout_ref<NEED_GAP, OCC>(ps, R, pvb, gb, P, ov, oc, rows, es, out, w, nullptr, pc);
       if (pass == 1) {
         a.res_gb[j] = out;
         break;
@@ -1435,6 +1450,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CLRRT_
     }
     __syncthreads();
     if (threadIdx.x < 3 && s_ctr[threadIdx.x]) atomicAdd(&a.ctr[threadIdx.x], s_ctr[threadIdx.x]);
+  }
+  if constexpr (OCC) {  // work counter 3: steps that took the grid's exact scan
+    if (a.ctr && oc.scans) atomicAdd(&a.ctr[3], (unsigned long long)oc.scans);
   }
 #ifdef CLRRT_ROLL_PROFILE
   if (a.ctr && j < a.njobs && gt % js == 0)
@@ -1668,12 +1686,16 @@ constexpr int kFinSuspend = 1000;  // k_roll_run: `fin` of a lane whose chain re
 // the per-wave LDS scratch after the obstacle tables at a.coop_off)
 // CARRY: the launch resumes / suspends chains (deferred samples, option defer_steps); the instantiation without
 // it has none of that code (the step loop's register allocation is that of the plain kernel)
-template <bool NEED_GAP, bool COOP, bool CARRY>
+// OCC: CLRRT_COLLISION_OCC with a grid set -- the step tests the occupancy grid (clrrt_occ.hpp) before the obstacle
+// list; the instantiations without it are the mode-1 kernels, none of that code in them
+template <bool NEED_GAP, bool COOP, bool CARRY, bool OCC = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CLRRT_ROLL_WAVES))) k_roll_run(RollArgs a,
                                                   int* __restrict__ qnext, int* __restrict__ best, int B) {
   extern __shared__ float4 lds[];
   glibc::stage_tables();
   const ObsView ov = stage_obstacles<NEED_GAP>(a, lds);
+  OccView oc{};
+  if constexpr (OCC) oc = occ_stage(a.occ, lds);
   CLRRT_PARAMS_DECL(P);
   const int lane = threadIdx.x & 63;
   CoopLds cl{};
@@ -1974,7 +1996,14 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CLRRT_
       d2 = roll_step_pre(r, P, c7, c8, c9, w, pc);
     }
     double Dobs;
-    if constexpr (COOP) {
+    if constexpr (OCC && COOP) {  // a lane whose step hits the grid sits the cooperative box tests out
+      const bool hit = act && occ_hit(oc, r.x0 + 1.424 * r.c2, r.x1 + 1.424 * r.s2, r.x2, r.c2, r.s2);
+      Dobs = obs_distance_coop(act && !hit, r, P, ov, w.box, cl, a.ctr ? a.ctr + 33 : nullptr);
+      if (!act) continue;
+      if (hit) Dobs = 0.0;
+    } else if constexpr (OCC) {
+      Dobs = obs_distance_occ<NEED_GAP>(r, P, ov, oc, w.box);
+    } else if constexpr (COOP) {
       Dobs = obs_distance_coop(act, r, P, ov, w.box, cl, a.ctr ? a.ctr + 33 : nullptr);
       if (!act) continue;
     } else {
@@ -2016,6 +2045,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CLRRT_
       atomicAdd(&a.ctr[0], v0);
       atomicAdd(&a.ctr[1], v1);
       atomicAdd(&a.ctr[2], v2);
+    }
+    if constexpr (OCC) {  // work counter 3: steps that took the grid's exact scan
+      unsigned long long v3 = oc.scans;
+#pragma unroll
+      for (int q = 32; q > 0; q >>= 1) v3 += (unsigned long long)__shfl_xor((long long)v3, q, 64);
+      if (lane == 0 && v3) atomicAdd(&a.ctr[3], v3);
     }
     if (n_rep) {  // replays run, replays whose row count differs from the committed node's (must stay 0)
       atomicAdd(&a.ctr[60], n_rep);
@@ -2601,8 +2636,10 @@ __global__ void __launch_bounds__(256) k_path_transform(clrrt_node* __restrict__
 // initializeTree rrtplanner.cpp:39-95 + getNodeCost :104-119, one workgroup (a committed path is
 // a few nodes / a few thousand rows: latency, not throughput).  Row checks run across the block;
 // the cost recurrence (costS float, read back as the next node's double parent cost) on lane 0.
+template <bool OCC>
 __global__ void __launch_bounds__(256) k_tree_reinit(ReinitArgs a) {
   glibc::stage_tables();
+  OccView oc{&a.occ, a.occ.occ, a.occ.reach, 0u};  // (OCC: the maps are read from global memory)
   __shared__ int s_kept, s_coll;
   __shared__ long long s_rows;
   const int tid = threadIdx.x;
@@ -2654,7 +2691,9 @@ __global__ void __launch_bounds__(256) k_tree_reinit(ReinitArgs a) {
       r.x0 = x[0]; r.x1 = x[1]; r.x2 = x[2]; r.x6 = x[6];
       glibc::sincos(r.x2, r.s2, r.c2);
       uint32_t tests = 0;
-      const double Dobs = obs_distance<true>(r, p, ov, tests);
+      double Dobs;
+      if constexpr (OCC) Dobs = obs_distance_occ<true>(r, p, ov, oc, tests);
+      else Dobs = obs_distance<true>(r, p, ov, tests);
       if (Dobs == 0) s_coll = 1;
       const double kappa = glibc::tan(x[3]) / p.L;
       double term = p.W0 * x[4] * p.dt + p.W1 * fabs(kappa);
@@ -2927,8 +2966,9 @@ __global__ void k_selftest_units(int unit, const double* __restrict__ in, const 
 // checkObsDistance(x) (collision.h:41; stub collisioncheck.cpp:6-8 or the OBB form
 // old_collisioncheck.cpp:24-51 under CLRRT_COLLISION_OBB) for n states of 10 doubles: the documented
 // collision hook, evaluated by the rollout kernels' own collision code (every obstacle, gap value kept).
+template <bool OCC>
 __global__ void k_obs_distance(DevParams p, const BakedObs* __restrict__ obs, const double* __restrict__ st, int n,
-                               double* __restrict__ out) {
+                               double* __restrict__ out, OccGrid og) {
   glibc::stage_tables();
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -2939,7 +2979,12 @@ __global__ void k_obs_distance(DevParams p, const BakedObs* __restrict__ obs, co
   r.x0 = x[0]; r.x1 = x[1]; r.x2 = x[2]; r.x6 = x[6];
   glibc::sincos(r.x2, r.s2, r.c2);
   uint32_t tests = 0;
-  out[i] = obs_distance<true>(r, p, ov, tests);
+  if constexpr (OCC) {
+    OccView oc{&og, og.occ, og.reach, 0u};
+    out[i] = obs_distance_occ<true>(r, p, ov, oc, tests);
+  } else {
+    out[i] = obs_distance<true>(r, p, ov, tests);
+  }
 }
 
 // Test hook (clrrt_selftest_collision): the rollout kernels' collision decision for explicit states, one state
@@ -2947,6 +2992,7 @@ __global__ void k_obs_distance(DevParams p, const BakedObs* __restrict__ obs, co
 // holds what k_roll_run's holds: the obstacle tables (stage_obstacles<false>) and, at a.coop_off, each wave's
 // cooperative scratch.  Control flow is wave-uniform up to the collision call (obs_distance_coop is entered by
 // every lane of the wave, a lane without a state or with active 0 as act = false).
+template <bool OCC>
 __global__ void __launch_bounds__(256) k_selftest_collision(RollArgs a, int path, const double* __restrict__ st,
                                                             const int32_t* __restrict__ active, int n,
                                                             double* __restrict__ dist, uint32_t* __restrict__ tests) {
@@ -2956,6 +3002,8 @@ __global__ void __launch_bounds__(256) k_selftest_collision(RollArgs a, int path
              a.p.coll_mode == CLRRT_COLLISION_OBB ? a.p.n_obs : 0, 0, 0, 0, 0.f, 0.f, 0.f};
   if (path != CLRRT_COLL_EXHAUSTIVE) ov = stage_obstacles<false>(a, lds);
   if (path == CLRRT_COLL_LANE_NOGRID) ov.gw = ov.gh = 0;
+  OccView oc{};
+  if constexpr (OCC) oc = occ_stage(a.occ, lds);  // where a k_roll_run launch of these arguments holds the maps
   CLRRT_PARAMS_DECL(P);
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   const bool act = i < n && active[i] != 0;
@@ -2977,10 +3025,16 @@ __global__ void __launch_bounds__(256) k_selftest_collision(RollArgs a, int path
     cl.hit = (int*)(base + 64 * sizeof(Box4) + 64 * sizeof(double));
     cl.q = (uint32_t*)(base + 64 * sizeof(Box4) + 64 * sizeof(double) + 64 * sizeof(int));
     cl.cap = COOP_QCAP;
-    const double Dc = obs_distance_coop(act, r, P, ov, cnt, cl);
-    if (act) D = Dc;
+    bool hit = false;
+    if constexpr (OCC) hit = act && occ_hit(oc, r.x0 + 1.424 * r.c2, r.x1 + 1.424 * r.s2, r.x2, r.c2, r.s2);
+    const double Dc = obs_distance_coop(act && !hit, r, P, ov, cnt, cl);
+    if (act) D = hit ? 0.0 : Dc;
   } else if (act) {
-    D = path == CLRRT_COLL_EXHAUSTIVE ? obs_distance<true>(r, P, ov, cnt) : obs_distance<false>(r, P, ov, cnt);
+    if constexpr (OCC)
+      D = path == CLRRT_COLL_EXHAUSTIVE ? obs_distance_occ<true>(r, P, ov, oc, cnt)
+                                        : obs_distance_occ<false>(r, P, ov, oc, cnt);
+    else
+      D = path == CLRRT_COLL_EXHAUSTIVE ? obs_distance<true>(r, P, ov, cnt) : obs_distance<false>(r, P, ov, cnt);
   }
   if (i < n) {
     dist[i] = D;
@@ -3192,10 +3246,54 @@ bool roll_coop_applies(const RollArgs& a) {
   return a.coop_enable && !a.p.need_gap && a.p.coll_mode == CLRRT_COLLISION_OBB && a.p.n_obs > 0 && a.grid.gw > 0 &&
          roll_obs_lds(a) + 4 * kCoopLdsPerWave <= 148 * 1024;
 }
+static size_t occ_place(OccGrid& g, size_t base, bool coop);
+bool roll_occ_in_lds(const RollArgs& a) {
+  OccGrid g = a.occ;
+  const bool coop = roll_coop_applies(a);
+  occ_place(g, roll_obs_lds(a) + (coop ? 4 * kCoopLdsPerWave : 0), coop);
+  return g.in_lds != 0;
+}
+
+// The occupancy maps' place in a rollout launch's dynamic LDS: behind `base` bytes of obstacle tables and
+// cooperative scratch when the whole stays within the 148 KB the kernels use beside the glibc tables' static LDS;
+// else the kernels read them from global memory.  The cooperative scratch counts whether the launch uses it or not
+// (`coop`: it does), so a grid's placement does not flip with the shape of the obstacle list.  Returns the launch's
+// dynamic LDS bytes.
+size_t occ_map_bytes(const OccGrid& g) { return sizeof(uint32_t) * ((size_t)g.h * g.ws + (size_t)g.rh * g.rws); }
+static size_t occ_place(OccGrid& g, size_t base, bool coop) {
+  g.in_lds = 0;
+  g.lds_off = 0;
+  if (g.w <= 0) return base;
+  const size_t off = (base + 15) / 16 * 16;
+  if (off + (coop ? 0 : 4 * kCoopLdsPerWave) + occ_map_bytes(g) > 148 * 1024) return base;
+  g.in_lds = 1;
+  g.lds_off = (int)off;
+  return off + occ_map_bytes(g);
+}
+
+template <int SRC>
+static hipError_t launch_roll_occ(hipStream_t st, const RollArgs& a0) {
+  RollArgs a = a0;
+  const size_t lds = occ_place(a.occ, a.p.need_gap ? 0 : roll_lds_bytes(a), false);
+  const int64_t threads = (int64_t)a.njobs * (a.job_stride > 1 ? a.job_stride : 1);
+  dim3 grid((unsigned)((threads + 255) / 256)), block(256);
+  const void* fn = a.p.need_gap ? (const void*)&k_rollout<SRC, true, true> : (const void*)&k_rollout<SRC, false, true>;
+  if (lds > 64 * 1024) {
+    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
+  if (a.p.need_gap)
+    hipLaunchKernelGGL((k_rollout<SRC, true, true>), grid, block, lds, st, a);
+  else
+    hipLaunchKernelGGL((k_rollout<SRC, false, true>), grid, block, lds, st, a);
+  LAUNCH_CHECK();
+  return hipSuccess;
+}
 
 template <int SRC>
 static hipError_t launch_roll_t(hipStream_t st, const RollArgs& a) {
   if (a.njobs <= 0) return hipSuccess;
+  if (a.occ.w > 0) return launch_roll_occ<SRC>(st, a);
   const size_t lds = roll_lds_bytes(a);
   const int64_t threads = (int64_t)a.njobs * (a.job_stride > 1 ? a.job_stride : 1);
   dim3 grid((unsigned)((threads + 255) / 256)), block(256);
@@ -3260,9 +3358,13 @@ hipError_t launch_rollout_persistent(hipStream_t st, const RollArgs& a0, int B, 
   const size_t obs_lds = roll_obs_lds(a0);
   const bool coop = roll_coop_applies(a);
   a.coop_off = (int)obs_lds;
-  const size_t lds = obs_lds + (coop ? 4 * kCoopLdsPerWave : 0);
+  const bool occ = a.occ.w > 0;  // CLRRT_COLLISION_OCC with a grid: the OCC instantiations
+  const size_t lds = occ_place(a.occ, obs_lds + (coop ? 4 * kCoopLdsPerWave : 0), coop);
   const bool carry = a.cap > 0 || a.ncarry > 0;  // deferred samples: the CARRY instantiation
-  const void* fn = a.p.need_gap ? (carry ? (const void*)&k_roll_run<true, false, true> : (const void*)&k_roll_run<true, false, false>)
+  const void* fn = occ ? (a.p.need_gap ? (carry ? (const void*)&k_roll_run<true, false, true, true> : (const void*)&k_roll_run<true, false, false, true>)
+                          : coop       ? (carry ? (const void*)&k_roll_run<false, true, true, true> : (const void*)&k_roll_run<false, true, false, true>)
+                                       : (carry ? (const void*)&k_roll_run<false, false, true, true> : (const void*)&k_roll_run<false, false, false, true>))
+                   : a.p.need_gap ? (carry ? (const void*)&k_roll_run<true, false, true> : (const void*)&k_roll_run<true, false, false>)
                    : coop       ? (carry ? (const void*)&k_roll_run<false, true, true> : (const void*)&k_roll_run<false, true, false>)
                                 : (carry ? (const void*)&k_roll_run<false, false, true> : (const void*)&k_roll_run<false, false, false>);
   if (lds > 64 * 1024 && (e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != hipSuccess)
@@ -3287,7 +3389,22 @@ hipError_t launch_rollout_persistent(hipStream_t st, const RollArgs& a0, int B, 
   } else {
     a.perm = nullptr;
   }
-  if (carry) {
+  if (occ) {
+    if (carry) {
+      if (a.p.need_gap)
+        hipLaunchKernelGGL((k_roll_run<true, false, true, true>), dim3(nb), dim3(256), lds, st, a, qnext, best, B);
+      else if (coop)
+        hipLaunchKernelGGL((k_roll_run<false, true, true, true>), dim3(nb), dim3(256), lds, st, a, qnext, best, B);
+      else
+        hipLaunchKernelGGL((k_roll_run<false, false, true, true>), dim3(nb), dim3(256), lds, st, a, qnext, best, B);
+    } else if (a.p.need_gap) {
+      hipLaunchKernelGGL((k_roll_run<true, false, false, true>), dim3(nb), dim3(256), lds, st, a, qnext, best, B);
+    } else if (coop) {
+      hipLaunchKernelGGL((k_roll_run<false, true, false, true>), dim3(nb), dim3(256), lds, st, a, qnext, best, B);
+    } else {
+      hipLaunchKernelGGL((k_roll_run<false, false, false, true>), dim3(nb), dim3(256), lds, st, a, qnext, best, B);
+    }
+  } else if (carry) {
     if (a.p.need_gap)
       hipLaunchKernelGGL((k_roll_run<true, false, true>), dim3(nb), dim3(256), lds, st, a, qnext, best, B);
     else if (coop)
@@ -3465,9 +3582,12 @@ hipError_t launch_selftest_units(hipStream_t st, int unit, const double* in, con
 }
 
 hipError_t launch_obs_distance(hipStream_t st, const DevParams& p, const BakedObs* obs, const double* states, int n,
-                               double* out) {
+                               double* out, const OccGrid* occ) {
   if (n <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_obs_distance, dim3((n + 255) / 256), dim3(256), 0, st, p, obs, states, n, out);
+  if (occ && occ->w > 0)
+    hipLaunchKernelGGL(k_obs_distance<true>, dim3((n + 255) / 256), dim3(256), 0, st, p, obs, states, n, out, *occ);
+  else
+    hipLaunchKernelGGL(k_obs_distance<false>, dim3((n + 255) / 256), dim3(256), 0, st, p, obs, states, n, out, OccGrid{});
   LAUNCH_CHECK();
   return hipSuccess;
 }
@@ -3479,13 +3599,19 @@ hipError_t launch_selftest_collision(hipStream_t st, const RollArgs& a0, int pat
   // the LDS of k_roll_run (launch_rollout_persistent): obstacle tables, then the four waves' cooperative scratch
   const size_t obs_lds = path == CLRRT_COLL_EXHAUSTIVE ? 0 : (roll_lds_bytes(a) + 15) / 16 * 16;
   a.coop_off = (int)obs_lds;
-  const size_t lds = obs_lds + (path == CLRRT_COLL_COOP ? 4 * kCoopLdsPerWave : 0);
+  const bool occ = a.occ.w > 0;
+  const size_t lds = occ_place(a.occ, obs_lds + (path == CLRRT_COLL_COOP ? 4 * kCoopLdsPerWave : 0),
+                               path == CLRRT_COLL_COOP);
   hipError_t e;
-  if (lds > 64 * 1024 && (e = hipFuncSetAttribute((const void*)&k_selftest_collision,
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != hipSuccess)
+  const void* fn = occ ? (const void*)&k_selftest_collision<true> : (const void*)&k_selftest_collision<false>;
+  if (lds > 64 * 1024 && (e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != hipSuccess)
     return e;
-  hipLaunchKernelGGL(k_selftest_collision, dim3((n + 255) / 256), dim3(256), lds, st, a, path, states, active, n, dist,
-                     tests);
+  if (occ)
+    hipLaunchKernelGGL(k_selftest_collision<true>, dim3((n + 255) / 256), dim3(256), lds, st, a, path, states, active, n,
+                       dist, tests);
+  else
+    hipLaunchKernelGGL(k_selftest_collision<false>, dim3((n + 255) / 256), dim3(256), lds, st, a, path, states, active, n,
+                       dist, tests);
   LAUNCH_CHECK();
   return hipSuccess;
 }
@@ -3521,8 +3647,22 @@ hipError_t launch_path_transform(hipStream_t st, clrrt_node* nodes, int n, doubl
 }
 
 hipError_t launch_tree_reinit(hipStream_t st, const ReinitArgs& a) {
-  hipLaunchKernelGGL(k_tree_reinit, dim3(1), dim3(256), 0, st, a);
+  if (a.occ.w > 0)
+    hipLaunchKernelGGL(k_tree_reinit<true>, dim3(1), dim3(256), 0, st, a);
+  else
+    hipLaunchKernelGGL(k_tree_reinit<false>, dim3(1), dim3(256), 0, st, a);
   return hipGetLastError();
+}
+
+hipError_t launch_occ_bake(hipStream_t st, const uint8_t* cells, const OccGrid& g, double Rc, unsigned int* count) {
+  const int64_t np = (int64_t)g.h * g.ws * 32, nr = (int64_t)g.rh * g.rws * 32;  // whole waves per row (ws, rws even)
+  hipLaunchKernelGGL(k_occ_pack, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st, cells, g.w, g.h, g.ws,
+                     const_cast<uint32_t*>(g.occ), count);
+  LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_occ_reach, dim3((unsigned)((nr + 255) / 256)), dim3(256), 0, st, g.occ, g.w, g.h, g.ws, g.rk,
+                     g.rm, Rc, g.rw, g.rh, g.rws, const_cast<uint32_t*>(g.reach));
+  LAUNCH_CHECK();
+  return hipSuccess;
 }
 
 hipError_t launch_init_root(hipStream_t st, const double* state, clrrt_node* tree, NnRec* nn, double* arena) {

@@ -1,0 +1,152 @@
+// clrrt_occ.hpp -- the static occupancy grid of CLRRT_COLLISION_OCC: the bake kernels (cell bytes -> bit-packed
+// occupancy map + conservative reach map) and the per-step test of the rollout kernels.
+//
+// The decision (include/clrrt.h, clrrt_set_occupancy): with vp the vehicle box centre, (cs, sn) the heading's cosine
+// and sine, c the centre of an occupied cell, d = c - vp, u = d.x cs + d.y sn, v = d.y cs - d.x sn, the grid hits when
+// some occupied cell has |u| <= 2.424 + inflate and |v| <= 1 + inflate, all in double.  A non-finite vp or heading does
+// not hit.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "clrrt_internal.hpp"
+
+namespace clrrt {
+
+#define OCC_VEH_A 2.424 /* vehicle box half length (old_collisioncheck.cpp:34-36) */
+#define OCC_VEH_B 1.0   /* half width */
+
+// ------------------------------------------------------------------------------------------------ bake
+// Bytes -> bits: one lane per cell of a row padded to 64 cells (ws is even), so a wave's ballot is two whole words of
+// one row, stored by its first lane; the padding bits are 0.  The occupied cells are counted into *count.
+__global__ void __launch_bounds__(256) k_occ_pack(const uint8_t* __restrict__ cells, int w, int h, int ws,
+                                                  uint32_t* __restrict__ occ, unsigned int* __restrict__ count) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int rowbits = ws * 32;
+  const int64_t j = idx / rowbits;
+  const int i = (int)(idx % rowbits);
+  const bool on = j < h && i < w && cells[j * w + i] != 0;
+  const unsigned long long m = __ballot(on);
+  if ((threadIdx.x & 63) == 0 && j < h) {
+    uint32_t* o = occ + j * ws + (i >> 5);
+    o[0] = (uint32_t)m;
+    o[1] = (uint32_t)(m >> 32);
+    if (m) atomicAdd(count, (unsigned int)__popcll(m));
+  }
+}
+
+// The reach map.  Reach cell (ri, rj) is the square of rk x rk occupancy cells whose corner is cell
+// ((ri - rm) rk, (rj - rm) rk); in units of one occupancy cell from the grid's corner (x0, y0) it is
+// [ax, ax + rk] x [ay, ay + rk] with integers ax, ay, and the centre of cell (i, j) is (i + 0.5, j + 0.5).  Its bit is
+// set when some occupied centre lies within Rc (cells) of the square.
+//
+// Why the clear bits are safe (a superset of the states that can hit): a hit needs an occupied centre c with
+// |u| <= A + inflate and |v| <= B + inflate, so |c - vp| <= |(A, B) + inflate (1, 1)| <= sqrt(A^2 + B^2) + inflate
+// sqrt 2 = R.  A vp inside the square is then within R of c, so the square is within R of c.  Rc = (R + slack) / res
+// with slack = res / 64 + 1e-9 (|x0| + |y0| + the map's extent), far above what rounding can move: the step's lookup
+// floor((vp - rx0) / rres) and the cell centres x0 + (i + 0.5) res are each off by a few ulps of the coordinates
+// (clrrt_set_occupancy refuses a grid whose res is below 2^-30 of them).  The scan below visits a superset of the
+// centres within Rc of the square: every row whose centre line is within Rc of [ay, ay + rk] (one row of slack either
+// side), and on a row at distance dy the columns within sqrt(Rc^2 - dy^2) of [ax, ax + rk] (one column of slack).
+// A vp outside the map is more than rm rk >= Rc + rk cells from every centre: free.
+__global__ void __launch_bounds__(256) k_occ_reach(const uint32_t* __restrict__ occ, int w, int h, int ws, int rk, int rm,
+                                                   double Rc, int rw, int rh, int rws, uint32_t* __restrict__ reach) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int rowbits = rws * 32;
+  const int64_t rj = idx / rowbits;
+  const int ri = (int)(idx % rowbits);
+  bool on = false;
+  if (rj < rh && ri < rw) {
+    const double ax = (double)(ri - rm) * rk, ay = (double)(rj - rm) * rk;
+    const double jlo = floor(ay - Rc - 0.5) - 1.0, jhi = ceil(ay + rk + Rc - 0.5) + 1.0;
+    const int j0 = (int)fmax(jlo, 0.0), j1 = (int)fmin(jhi, (double)(h - 1));
+    for (int j = j0; j <= j1 && !on; j++) {
+      const double y = j + 0.5;
+      const double dy = fmax(fmax(ay - y, y - (ay + rk)), 0.0);
+      const double s2 = Rc * Rc - dy * dy;
+      const double span = s2 > 0.0 ? sqrt(s2) : 0.0;  // (a slack row: its nearest columns only)
+      const double ilo = floor(ax - span - 0.5) - 1.0, ihi = ceil(ax + rk + span - 0.5) + 1.0;
+      if (ihi < 0.0 || ilo > (double)(w - 1)) continue;
+      const int i0 = (int)fmax(ilo, 0.0), i1 = (int)fmin(ihi, (double)(w - 1));
+      const uint32_t* row = occ + (int64_t)j * ws;
+      for (int q = i0 >> 5; q <= (i1 >> 5); q++) {
+        uint32_t m = row[q];
+        if (q == (i0 >> 5)) m &= ~0u << (i0 & 31);
+        if (q == (i1 >> 5)) m &= ~0u >> (31 - (i1 & 31));
+        if (m) { on = true; break; }
+      }
+    }
+  }
+  const unsigned long long m = __ballot(on);
+  if ((threadIdx.x & 63) == 0 && rj < rh) {
+    uint32_t* o = reach + rj * rws + (ri >> 5);
+    o[0] = (uint32_t)m;
+    o[1] = (uint32_t)(m >> 32);
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ step test
+// The maps a kernel reads: the grid record (a kernel argument: scalar loads) and the two bitmaps, in LDS
+// (occ_stage) or global memory; scans counts the lane's steps that took the exact scan.
+struct OccView {
+  const OccGrid* g;
+  const uint32_t* occ;
+  const uint32_t* reach;
+  uint32_t scans;
+};
+
+// Copies both maps into the block's dynamic LDS at g.lds_off when the launch placed them there (every thread of
+// the block calls it; the caller's next barrier, or this one, orders the copy before the first step).
+__device__ __forceinline__ OccView occ_stage(const OccGrid& g, void* lds_base) {
+  OccView v{&g, g.occ, g.reach, 0u};
+  if (g.in_lds) {
+    uint32_t* o = (uint32_t*)((char*)lds_base + g.lds_off);
+    const int no = g.h * g.ws, nr = g.rh * g.rws;
+    for (int q = threadIdx.x; q < no; q += blockDim.x) o[q] = g.occ[q];
+    for (int q = threadIdx.x; q < nr; q += blockDim.x) o[no + q] = g.reach[q];
+    __syncthreads();
+    v.occ = o;
+    v.reach = o + no;
+  }
+  return v;
+}
+
+// One step's grid decision for the vehicle box centre (vpx, vpy) and heading th with cosine cs and sine sn: the
+// reach-map bit at vp (clear: free, the open-space path), else the occupied cells inside the axis-aligned bounds
+// of the inflated box (one cell of slack: the exact test below decides), taken word by word and bit by bit.
+__device__ __forceinline__ bool occ_hit(OccView& ov, double vpx, double vpy, double th, double cs, double sn) {
+  const OccGrid& g = *ov.g;
+  if (!(isfinite(vpx) && isfinite(vpy) && isfinite(th))) return false;
+  const double fx = (vpx - g.rx0) / g.rres, fy = (vpy - g.ry0) / g.rres;
+  if (!(fx >= 0.0 && fx < (double)g.rw && fy >= 0.0 && fy < (double)g.rh)) return false;
+  const int ix = (int)fx, iy = (int)fy;
+  if (!((ov.reach[iy * g.rws + (ix >> 5)] >> (ix & 31)) & 1u)) return false;
+  ov.scans++;
+  const double A = OCC_VEH_A + g.inflate, B = OCC_VEH_B + g.inflate;
+  const double ex = fabs(cs) * A + fabs(sn) * B, ey = fabs(sn) * A + fabs(cs) * B;
+  // (vp lies inside the reach map, so these quotients are small numbers: the casts are in range)
+  const double ilo = floor((vpx - ex - g.x0) / g.res - 0.5) - 1.0, ihi = ceil((vpx + ex - g.x0) / g.res - 0.5) + 1.0;
+  const double jlo = floor((vpy - ey - g.y0) / g.res - 0.5) - 1.0, jhi = ceil((vpy + ey - g.y0) / g.res - 0.5) + 1.0;
+  if (ihi < 0.0 || jhi < 0.0 || ilo > (double)(g.w - 1) || jlo > (double)(g.h - 1)) return false;
+  const int i0 = (int)fmax(ilo, 0.0), i1 = (int)fmin(ihi, (double)(g.w - 1));
+  const int j0 = (int)fmax(jlo, 0.0), j1 = (int)fmin(jhi, (double)(g.h - 1));
+  for (int j = j0; j <= j1; j++) {
+    const double dy = (g.y0 + (j + 0.5) * g.res) - vpy;
+    const uint32_t* row = ov.occ + j * g.ws;
+    for (int q = i0 >> 5; q <= (i1 >> 5); q++) {
+      uint32_t m = row[q];
+      if (q == (i0 >> 5)) m &= ~0u << (i0 & 31);
+      if (q == (i1 >> 5)) m &= ~0u >> (31 - (i1 & 31));
+      while (m) {
+        const int i = q * 32 + __builtin_ctz(m);
+        m &= m - 1;
+        const double dx = (g.x0 + (i + 0.5) * g.res) - vpx;
+        const double u = dx * cs + dy * sn, v = dy * cs - dx * sn;
+        if (fabs(u) <= A && fabs(v) <= B) return true;
+      }
+    }
+  }
+  return false;
+}
+
+}  // namespace clrrt

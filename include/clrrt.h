@@ -62,6 +62,7 @@ extern "C" {
 /* ---- collision modes ---- */
 #define CLRRT_COLLISION_STUB 0 /* checkObsDistance returns 100 (rrt/src/collisioncheck.cpp:6-8) */
 #define CLRRT_COLLISION_OBB 1  /* OBB separating-axis test (rrt/src/old_collisioncheck.cpp:6-148) */
+#define CLRRT_COLLISION_OCC 2  /* the static occupancy grid (clrrt_set_occupancy), then the OBB test of mode 1 */
 
 /* ---- rollout outcomes (Simulation flags + the fail_* counter it bumped) ---- */
 #define CLRRT_ROLL_ITERLIMIT 0 /* horizon exhausted: fail_iterlimit (simulation.cpp:142) */
@@ -221,6 +222,42 @@ int clrrt_set_params(clrrt_ctx* ctx, const clrrt_params* p);
  * centre, moved by 3600 s of its velocity, plus its bounding radius and 16 m reaches 2^15 m in either coordinate is
  * exempt from culling (tested at every step): out there a float ulp is no longer small against the culls' margin. */
 int clrrt_set_obstacles(clrrt_ctx* ctx, const clrrt_obstacle* obs, int32_t m);
+/* The static occupancy grid of CLRRT_COLLISION_OCC, in the car frame of the query (engine extension: the input
+ * MotionPlanner::updateObstacles' notes ask for, motionplanner.cpp:80-82).  Cell (i, j), 0 <= i < w, 0 <= j < h, is
+ * occupied when cells[j w + i] != 0; its centre is c = (x0 + (i + 0.5) res, y0 + (j + 0.5) res).  For a state x with
+ * the vehicle box centre vp = (x[0] + 1.424 cos x[2], x[1] + 1.424 sin x[2]), d = c - vp, u = d.x cos + d.y sin and
+ * v = d.y cos - d.x sin, the grid hits when some occupied cell has |u| <= 2.424 + inflate and |v| <= 1 + inflate
+ * (double arithmetic throughout); a non-finite vp or heading does not hit.  On a hit checkObsDistance is 0 (the
+ * rollout fails with fail_collision; no box test is made or counted); otherwise it is what CLRRT_COLLISION_OBB gives
+ * for the same state and obstacle list.  The grid does not move with obs_use_pred; moving obstacles stay boxes.
+ * Mode 2 without a grid is mode 1. */
+typedef struct {
+  double x0, y0;   /* car-frame position of the corner of cell (0, 0) */
+  double res;      /* cell size [m], > 0 */
+  double inflate;  /* added to both half extents of the vehicle box [m], >= 0 */
+  int32_t w, h;    /* cells per row, rows: each <= 2048, w h <= 2^22 */
+} clrrt_occupancy;
+/* Sets (copies and bakes on the device) the grid; occ == NULL or occ->w == 0 clears it.  CLRRT_EINVAL names the field
+ * at fault in clrrt_last_error: w, h out of range, a non-finite x0 / y0, res not finite and > 0 (or below 2^-30 of
+ * the grid's coordinates), inflate not finite and >= 0 (or above 1000), cells NULL.  Like clrrt_set_obstacles it first
+ * lands the deferred rows of committed nodes (they were committed against the old scene).  Legal in any collision
+ * mode; the grid is read only in mode 2.  Under sharding every rank sets the same grid. */
+int clrrt_set_occupancy(clrrt_ctx* ctx, const clrrt_occupancy* occ, const uint8_t* cells);
+/* The grid as baked.  placement: where the persistent rollout kernel of the current parameters and obstacles
+ * holds the two bitmaps. */
+#define CLRRT_OCC_NONE 0
+#define CLRRT_OCC_LDS 1
+#define CLRRT_OCC_GLOBAL 2
+typedef struct {
+  int32_t w, h;            /* 0, 0: no grid */
+  int32_t reach_w, reach_h; /* reach map cells */
+  int32_t reach_k;         /* occupancy cells per reach cell side */
+  int32_t placement;       /* CLRRT_OCC_* */
+  int64_t occupied;        /* occupied cells */
+  int64_t map_bytes;       /* both bitmaps */
+  double bake_ms;          /* device time of the last bake (upload + kernels) */
+} clrrt_occupancy_info_t;
+int clrrt_occupancy_info(clrrt_ctx* ctx, clrrt_occupancy_info_t* out);
 int clrrt_set_rank(clrrt_ctx* ctx, int32_t rank);
 
 /* ---- tree ---- */
@@ -423,7 +460,8 @@ int clrrt_round_eval_lists(clrrt_ctx* ctx, const clrrt_sample* samples, int32_t 
  * hook README.md:40-47): out[i] = the distance the context's collision mode gives for states[i] (10
  * doubles: x, y, theta, ..., t in column 6) — 100 under CLRRT_COLLISION_STUB
  * (collisioncheck.cpp:6-8), the OBB form of old_collisioncheck.cpp:24-51 (0 on overlap, else the
- * smallest first-separating-axis gap, 10000 without obstacles) under CLRRT_COLLISION_OBB.  Evaluated on
+ * smallest first-separating-axis gap, 10000 without obstacles) under CLRRT_COLLISION_OBB; under
+ * CLRRT_COLLISION_OCC 0 where the occupancy grid hits (clrrt_set_occupancy), else mode 1's value.  Evaluated on
  * the device by the rollout kernels' own collision code. */
 int clrrt_obstacle_distance(clrrt_ctx* ctx, const double* states, int32_t n, double* out);
 
@@ -535,7 +573,8 @@ int clrrt_get_counters(clrrt_ctx* ctx, clrrt_counters* out);
 int clrrt_reset_counters(clrrt_ctx* ctx);
 /* Algorithmic work done by rollout kernels since the last reset (SURVEY §8(d) roofline basis):
  * out[0] = simulated steps (incl. speculative candidates), out[1] = reference
- * points scanned by findClosestPoint, out[2] = OBB box tests (first overlap ends a step's scan). */
+ * points scanned by findClosestPoint, out[2] = OBB box tests (first overlap ends a step's scan).
+ * (Raw counter 3, clrrt_debug_counters: steps of CLRRT_COLLISION_OCC that took the grid's exact scan.) */
 int clrrt_work_counters(clrrt_ctx* ctx, int64_t out[3]);
 
 /* Launch-time profile of the last clrrt_expand / round call: device milliseconds per kernel
@@ -587,7 +626,7 @@ int clrrt_walk_audit(clrrt_ctx* ctx, const clrrt_sample* samples, int32_t n, int
  * *n = the count.  With deferred samples, round r's samples are evaluated against the tree of out[r - 1] nodes (the
  * tree before the expansion for r = 0) and appended by the commit that is due for them. */
 int clrrt_round_sizes(clrrt_ctx* ctx, int64_t* out, int64_t cap, int64_t* n);
-/* Diagnostics: the context's 64 raw work counters (0..2 rollout work, 8..39 search statistics,
+/* Diagnostics: the context's 64 raw work counters (0..2 rollout work, 3 occupancy-grid exact scans, 8..39 search statistics,
  * 40..63 rollout profile counters of a -DCLRRT_ROLL_PROFILE build: 40..47 per-phase clocks, 48..51 wave
  * lifetimes (sum, max), busiest lane's steps, waves, 52..55 queue-drain times and tail steps).
  * With option "nn_delta_verify" (lag-2 BATCH rounds, a build without the rollout profile): 38 = samples whose

@@ -176,6 +176,14 @@ class Engine {
     det_set_ = true;
   }
 
+  /* The static occupancy grid of CLRRT_COLLISION_OCC (clrrt_set_occupancy; car frame): cells = h rows of w bytes,
+   * non-zero = occupied; occ.w == 0 or cells == nullptr clears it.  Read only when params().collision_mode is 2. */
+  void setOccupancy(const clrrt_occupancy& occ, const uint8_t* cells) {
+    drop_cache();
+    const bool clear = occ.w == 0 || !cells;
+    check(ctx_, clrrt_set_occupancy(ctx_, clear ? nullptr : &occ, clear ? nullptr : cells), "clrrt_set_occupancy");
+  }
+
   /* The device tree := RRT.tree (e.g. after MyRRT::addInitialNode or initializeTree). */
   template <class RRTT>
   void load_tree(const RRTT& rrt) {
@@ -719,6 +727,11 @@ struct TreeMarker {             /* createStateMsg(nodeid, tree[nodeid].tra, goal
   std::vector<double> rows;     /* nrows x 10 */
 };
 
+struct OccupancyGrid {          /* the static world as a lidar / camera occupancy grid, in the car frame of the query */
+  clrrt_occupancy dims = {0, 0, 0, 0, 0, 0};  /* corner, cell size, inflate, w, h (include/clrrt.h); w == 0: none */
+  std::vector<uint8_t> cells;   /* h rows of w bytes, non-zero = occupied */
+};
+
 struct PlanReport {
   int32_t reinit_outcome = -1;  /* CLRRT_REINIT_* of initializeTree */
   int64_t iterations = 0;       /* expandTree iterations of the Timer loop */
@@ -733,7 +746,8 @@ struct PlanReport {
 class MotionPlanner {
  public:
   struct Config {
-    clrrt_params base;          /* vehicle, gains, weights, collision mode (goal/vmax/ref_res set per query) */
+    clrrt_params base;          /* vehicle, gains, weights, collision mode -- CLRRT_COLLISION_OCC (2) tests the grid of
+                                 * updateOccupancy, then the detections (goal/vmax/ref_res set per query) */
     clrrt_capacity cap;
     bool commit_path = true;    /* motionplanner/commit_path */
     int32_t mode = CLRRT_MODE_BATCH;
@@ -781,6 +795,15 @@ class MotionPlanner {
     det_.clear();
     for (const auto& d : det) det_.push_back(obstacle_to_c(d));
   }
+  /* The occupancy-grid form of updateObstacles (the note at motionplanner.cpp:80-82): the static world in the car
+   * frame of the next query, applied at the next planMotion beside the detections (which stay boxes); an empty grid
+   * (dims.w == 0) clears it.  Under sharding every rank is given the same grid. */
+  void updateOccupancy(const OccupancyGrid& grid) {
+    if (grid.dims.w != 0 && grid.cells.size() < (size_t)grid.dims.w * (size_t)std::max(grid.dims.h, 0))
+      throw Error("updateOccupancy: fewer than w * h cells");
+    grid_ = grid;
+    grid_dirty_ = true;
+  }
 
   /* One query.  Returns false when no path was found ("No solution found", :56-58): the committed path
    * is then empty and the next query restarts from the car state. */
@@ -799,6 +822,12 @@ class MotionPlanner {
     for (int i = 0; i < 3; i++) p.Cxy[i] = i < (int)req.Cxy.size() ? req.Cxy[i] : 0.0;
     check(ctx_, clrrt_set_params(ctx_, &p), "clrrt_set_params");
     check(ctx_, clrrt_set_obstacles(ctx_, det_.data(), (int32_t)det_.size()), "clrrt_set_obstacles");  // RRT.det
+    if (grid_dirty_) {
+      const bool none = grid_.dims.w == 0;
+      check(ctx_, clrrt_set_occupancy(ctx_, none ? nullptr : &grid_.dims, none ? nullptr : grid_.cells.data()),
+            "clrrt_set_occupancy");
+      grid_dirty_ = false;
+    }
     check(ctx_, clrrt_path_transform(ctx_, CLRRT_WORLD_TO_CAR, world), "clrrt_path_transform");          // :22
     if (!cfg_.commit_path) check(ctx_, clrrt_path_commit(ctx_, nullptr, 0, nullptr), "clrrt_path_commit");  // :28-30
     int32_t oc = -1;
@@ -886,6 +915,8 @@ class MotionPlanner {
   clrrt_rng rng_;
   std::vector<double> state_;
   std::vector<clrrt_obstacle> det_;
+  OccupancyGrid grid_;
+  bool grid_dirty_ = false;
   int32_t (*completer_)(void*, clrrt_ctx*, int64_t*) = nullptr;
   void* completer_user_ = nullptr;
 };

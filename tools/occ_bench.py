@@ -1,0 +1,104 @@
+#!/usr/bin/env python3
+"""Occupancy-grid collision mode against the obstacle list on the cfg3 scene (200 static boxes): 16384 samples per
+round, 8 rounds, deferred samples as bench.py runs cfg3 (defer_steps 128).
+
+  mode 1   the boxes as CLRRT_COLLISION_OBB takes them (run it against another build with CLRRT_LIB=... to compare
+           two commits -- or, where the other build's binding differs too, with CLRRT_PKG=<its cl-rrt_amd
+           directory>: the mode-1 figures are what a change must leave alone)
+  mode 2   the same boxes rasterised at res 0.2 (scenes.rasterize), no obstacle list, CLRRT_COLLISION_OCC
+
+Per run: rollout-kernel ms per launch (clrrt_kernel_time family 1), the share of simulated steps that took the
+grid's exact scan (raw work counter 3 over work counter 0), nodes grown.  Then the bake time of 512 x 512 and
+2048 x 2048 grids (2 % random fill; clrrt_occupancy_info).  Writes a text summary (default profiles/occ_grid.txt).
+
+  python tools/occ_bench.py [--runs 3] [--modes 1,2] [--out profiles/occ_grid.txt] [--label text]
+"""
+import argparse
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.environ.get("CLRRT_PKG") or os.path.join(ROOT, "cl-rrt_amd"))  # CLRRT_PKG: another build's tree
+
+import clrrt  # noqa: E402
+from clrrt import abi, scenes  # noqa: E402
+
+B, ROUNDS, DEFER = 16384, 8, 128
+GRID = dict(x0=0.0, y0=-26.0, res=0.2, w=330, h=260)
+
+
+def grow(mode, obs, cells):
+    pl = clrrt.Planner(clrrt.default_params(collision_mode=mode), max_nodes=1 << 20, max_rows=1 << 26, max_batch=B,
+                       max_obstacles=max(1, len(obs)))
+    try:
+        pl.set_option("defer_steps", DEFER)
+        pl.set_obstacles(obs)
+        if cells is not None:
+            pl.set_occupancy(GRID["x0"], GRID["y0"], GRID["res"], cells)
+        pl.enable_timing(True)
+        pl.tree_init()
+        st = pl.expand(clrrt.Rng(1), n_iters=B * ROUNDS, mode=clrrt.CLRRT_MODE_BATCH, batch=B)
+        ms, launches = pl.kernel_time(1)
+        d = pl.debug_counters()
+        info = pl.occupancy_info() if cells is not None else None
+        return dict(ms_per_launch=ms / max(1, launches), launches=launches, steps=d[0], scans=d[3],
+                    nodes=pl.size()[0], rounds=st["rounds"], info=info)
+    finally:
+        pl.close()
+
+
+def bake(n, runs):
+    cells = (np.random.default_rng(n).random((n, n)) < 0.02).astype(np.uint8)
+    pl = clrrt.Planner(clrrt.default_params(collision_mode=abi.CLRRT_COLLISION_OCC), max_nodes=1 << 10,
+                       max_rows=1 << 14, max_batch=64)
+    try:
+        out = []
+        for _ in range(runs + 1):  # the first call allocates
+            pl.set_occupancy(-0.05 * n, -0.05 * n, 0.1, cells)
+            out.append(pl.occupancy_info())
+        return out[1:]
+    finally:
+        pl.close()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--runs", type=int, default=3)
+    ap.add_argument("--modes", default="1,2")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "occ_grid.txt"))
+    ap.add_argument("--label", default="")
+    args = ap.parse_args()
+    obs = scenes.urban_scene(200)
+    lines = [f"occ_bench {args.label}: cfg3 scene (200 static boxes), {B} samples x {ROUNDS} rounds, defer_steps {DEFER}; "
+             f"library {os.path.relpath(clrrt.LIB_PATH, ROOT)}"]
+    for mode in (int(m) for m in args.modes.split(",") if m):
+        if mode == 2 and not hasattr(abi, "CLRRT_COLLISION_OCC"):
+            continue
+        cells = scenes.rasterize(obs, **GRID) if mode == 2 else None
+        res = [grow(mode, obs if mode == 1 else obs[:0], cells) for _ in range(args.runs)]
+        ms = [r["ms_per_launch"] for r in res]
+        lines.append(f"mode {mode}: rollout kernel ms per launch {' '.join('%.3f' % v for v in ms)} (spread "
+                     f"{(max(ms) - min(ms)) / min(ms) * 100:.1f} %), launches {res[0]['launches']}, nodes "
+                     f"{res[0]['nodes']}, steps {res[0]['steps']}")
+        if mode == 2:
+            r = res[0]
+            lines.append(f"mode 2: grid {GRID['w']} x {GRID['h']} at res {GRID['res']}, {r['info']['occupied']} occupied "
+                         f"cells, maps {r['info']['map_bytes']} B in "
+                         f"{'LDS' if r['info']['placement'] == abi.OCC_LDS else 'global memory'}; exact scans "
+                         f"{r['scans']} of {r['steps']} steps ({100.0 * r['scans'] / max(1, r['steps']):.2f} %)")
+    if "2" in args.modes.split(","):
+        for n in (512, 2048):
+            b = bake(n, args.runs)
+            lines.append(f"bake {n} x {n} (2 % fill, {b[0]['occupied']} occupied, reach map {b[0]['reach_w']} x "
+                         f"{b[0]['reach_h']}): {' '.join('%.3f' % v['bake_ms'] for v in b)} ms (upload + kernels)")
+    text = "\n".join(lines) + "\n"
+    print(text, end="")
+    if args.out:
+        with open(args.out, "a") as f:
+            f.write(text)
+
+
+if __name__ == "__main__":
+    main()

@@ -44,6 +44,49 @@ struct DevBuf {
   size_t bytes = 0;
 };
 
+// One round's samples and candidate lists.  The context keeps three sets and names them by role (clrrt_ctx::ls).
+struct ListSet {
+  clrrt_sample* d_samples = nullptr;  // [max_batch]
+  clrrt_sample* h_samples = nullptr;  // [max_batch] pinned
+  int* cand = nullptr;                // [max_batch * CAND_K]
+  float* ckey = nullptr;              // [max_batch * CAND_K]
+  int* ncand = nullptr;               // [max_batch]
+  int* ctie = nullptr;                // [max_batch]
+  // lag-2 rounds only (lag_alloc)
+  hipEvent_t ev = nullptr;   // recorded after the set's merge
+  hipEvent_t evw = nullptr;  // recorded after its walk (the merge waits for it on the merge stream)
+  hipEvent_t evm = nullptr;  // recorded after the walk's main grid (and wseed)
+  float* wseed = nullptr;    // [max_batch] nn_delta_early: the appended-node search's caps, taken after the main grid
+};
+
+// Search region (the sampling region and the tree's box) and the float frame of the searches.
+struct NnSetup {
+  NnFrame fr;
+  double x0, y0, x1, y1;
+  bool region_ok;
+};
+
+// What a walk index was built for (n = -1: nothing): the tree size, the node range, the frame and region, the index
+// options.  Nodes never change once appended, so an index stays valid while all of these are the same.
+struct BuiltFor {
+  int64_t n = -1, first = 0, count = 0;
+  double ox = 0, oy = 0, x0 = 0, y0 = 0, x1 = 0, y1 = 0;
+  float delta = 0;
+  int kind = 0, hscale = 0;
+  void set(int64_t n_, int64_t first_, int64_t count_, const NnSetup& su, int kind_, int hscale_) {
+    n = n_; first = first_; count = count_;
+    ox = su.fr.ox; oy = su.fr.oy; delta = su.fr.delta;
+    x0 = su.x0; y0 = su.y0; x1 = su.x1; y1 = su.y1;
+    kind = kind_; hscale = hscale_;
+  }
+  bool matches(int64_t n_, int64_t first_, int64_t count_, const NnSetup& su, int kind_, int hscale_) const {
+    BuiltFor o;
+    o.set(n_, first_, count_, su, kind_, hscale_);
+    return n == o.n && first == o.first && count == o.count && ox == o.ox && oy == o.oy && delta == o.delta &&
+           x0 == o.x0 && y0 == o.y0 && x1 == o.x1 && y1 == o.y1 && kind == o.kind && hscale == o.hscale;
+  }
+};
+
 struct clrrt_ctx {
   int device = 0;
   int rank = 0;
@@ -74,14 +117,16 @@ struct clrrt_ctx {
   hipEvent_t occ_ev[2] = {nullptr, nullptr};
   float occ_bake_ms = 0.f;
   // round buffers (capacity cap.max_batch samples)
-  clrrt_sample* d_samples = nullptr;
+  // The list sets: sets[] owns the buffers (sets 0 and 1 from clrrt_create, set 2 and the lag-2 members of all three
+  // from lag_alloc; free_all frees sets[] alone), ls[] names them by role: ls[0] this round's set, ls[1] the set the
+  // side stream searches for the next round (lag 2: round r+1's, being merged), ls[2] lag 2's round r+2's, being
+  // searched.  ls[] is a permutation of &sets[0..2] at every instant, so any exit leaves a context safe to free and
+  // to reuse.
+  ListSet sets[3];
+  ListSet* ls[3] = {&sets[0], &sets[1], &sets[2]};
   float* pk = nullptr;
   int* pi = nullptr;
   int64_t partial_cap = 0;  // entries (samples * chunks * K)
-  int* cand = nullptr;
-  float* ckey = nullptr;
-  int* ncand = nullptr;
-  int* ctie = nullptr;
   KeyId* sort_scratch = nullptr;
   int64_t sort_cap = 0;  // KeyId entries
   RollRes* res_spec = nullptr;
@@ -149,10 +194,10 @@ struct clrrt_ctx {
   int nnw_double = 1;  // "nn_walk_double": build the next round's index while the side search runs
   WalkBufs nnw{};                      // allocated on first use
   // pipelined rounds: a second index set, so the next round's index is built while the side stream's
-  // search still reads this one (swapped in after each commit); nnw_built: the tree size and frame the
-  // current set's index was built for (n = -1: none)
+  // search still reads this one (swapped in after each commit); nnw_built: what the current set's index
+  // was built for (the whole tree: tree_index_matches)
   WalkBufs nnw_alt{};
-  struct { int64_t n = -1; double ox, oy, x0, y0, x1, y1; float delta; } nnw_built;
+  BuiltFor nnw_built;
   CompactBufs cmp{};                   // round compaction scratch
   // persistent rollouts (k_roll_run; k_roll_flag + k_roll_order for the queue order)
   int roll_persistent = 1;
@@ -214,8 +259,8 @@ struct clrrt_ctx {
   double* ri_terms = nullptr;  // [2 * path_rows_cap]
   double reg_x0 = 0, reg_y0 = 0, reg_x1 = 0, reg_y1 = 0;  // sampling region + margin
   // pipelined BATCH rounds (clrrt_expand): while a round's rollouts run on `stream`, the walk search
-  // of the next round's samples over the same tree runs on `side` into the *2 buffers; the round
-  // then merges in the nodes it appended (launch_nn_delta) and the buffers swap
+  // of the next round's samples over the same tree runs on `side` into the set ls[1]; the round
+  // then merges in the nodes it appended (launch_nn_delta) and ls[0] / ls[1] swap
   int nn_pipeline = 1;  // option "nn_pipeline"
   hipStream_t side = nullptr;
   // option "cu_split" (k = 1..7): the rollouts run on their own stream restricted to k/8 of the CUs and
@@ -225,29 +270,17 @@ struct clrrt_ctx {
   hipStream_t roll_st = nullptr;
   hipEvent_t ev_rs0 = nullptr, ev_rs1 = nullptr;
   hipEvent_t ev_tree = nullptr, ev_walk = nullptr, ev_commit = nullptr;
-  clrrt_sample* d_samples2 = nullptr;
-  clrrt_sample* h_samples2 = nullptr;
-  int* cand2 = nullptr;
-  float* ckey2 = nullptr;
-  int* ncand2 = nullptr;
-  int* ctie2 = nullptr;
   // option "nn_lag" (1 or 2; 0 = by query length): how many rounds ahead the pipelined BATCH rounds search
   // (2: expand_lag2).  The default picks 2 for long queries (a budget of >= 1 s or >= 64 rounds), 1 for
   // short ones: round-3 A/B, cfg3 (2 s) 1.031 vs 1.015 M nodes/s for lag 2; cfg2 (200 ms) 0.551 vs 0.565 M
   // for lag 1; cfg5 (200 ms) equal.  (With round 2's rollout kernel lag 1 was ahead on cfg3 too.)
-  // Lag 2 keeps a third list set (*3), a third walk index set and a second side stream (allocated on
+  // Lag 2 keeps a third list set (ls[2]), a third walk index set and a second side stream (allocated on
   // first use).
   int nn_lag = 0;
-  clrrt_sample* d_samples3 = nullptr;
-  clrrt_sample* h_samples3 = nullptr;
-  int* cand3 = nullptr;
-  float* ckey3 = nullptr;
-  int* ncand3 = nullptr;
-  int* ctie3 = nullptr;
   WalkBufs nnw3{};
   hipStream_t side2 = nullptr;
   // lag 2: the appended-node merges run on their own stream (mst), behind the commit and the slot's walk
-  // (events ev_lagw); with option "stream_prio" (default 1) the main and merge streams have the device's
+  // (its set's event evw); with option "stream_prio" (default 1) the main and merge streams have the device's
   // highest priority and the walk streams (side, side2) its lowest, so the commit and merge kernels are
   // not queued behind thousands of walk waves (kernel trace: k_select 16 us -> 1.9 ms late in a query)
   hipStream_t mst = nullptr;
@@ -264,16 +297,10 @@ struct clrrt_ctx {
   WalkBufs nnw_d{};
   // Tree-partitioned search (clrrt_nn_range): the walk over a node range [first, first + count) of any size has an
   // index set of its own (a full set, allocated on first use; launch_nn_walk_build with a node-id base), so the sets
-  // of the pipelined rounds (nnw, nnw_alt, nnw3, nnw_d) stay as they are.  nnr_built: what its index was built for
-  // (n = -1: nothing) -- nodes never change once appended, so it stays valid while the tree size, the range, the frame
-  // and the index options are the same; every call that replaces or drops nodes goes through pf_reset, which clears it.
+  // of the pipelined rounds (nnw, nnw_alt, nnw3, nnw_d) stay as they are.  nnr_built: what its index was built for;
+  // every call that replaces or drops nodes goes through pf_reset, which clears it.
   WalkBufs nnw_r{};
-  struct {
-    int64_t n = -1, first = 0, count = 0;
-    double ox, oy, x0, y0, x1, y1;
-    float delta;
-    int kind, hscale;
-  } nnr_built;
+  BuiltFor nnr_built;
   // clrrt_nn_merge's inputs on the device ([part][sample][CAND_K] ids / keys, [part][sample] counts; grown on demand)
   int* pm_ids = nullptr;
   float* pm_keys = nullptr;
@@ -284,7 +311,7 @@ struct clrrt_ctx {
   int* vpi = nullptr;
   float* vseed = nullptr;  // ... and its copy of the caps (k_nn_partial lowers them)
   // option "nn_delta_early" (default 1, round 6): the appended-node search of a slot starts after its walk's main grid
-  // (key caps from k_walk_seed, per slot in wseed) instead of after the overflow split and its merge, so it runs beside
+  // (key caps from k_walk_seed, in the set's wseed) instead of after the overflow split and its merge, so it runs beside
   // the split (a cfg3 trace: main grid done 1.7 ms before the rollout kernel, split until 0.6 ms after it, the search
   // after that until 1.9 ms, profiles/r06w_cfg3_list_crit.txt); the merge still waits for the whole walk.
   int nn_delta_early = 1;
@@ -292,16 +319,12 @@ struct clrrt_ctx {
   // lanes (k_nn_order), so explore lanes do not idle while optimize lanes compute exact keys
   int nn_lane_order = 1;
   int* nn_order = nullptr;  // [max_batch]
-  float* wseed[3] = {nullptr, nullptr, nullptr};      // per slot: [max_batch] caps taken after the main walk grid
-  hipEvent_t ev_wm[3] = {nullptr, nullptr, nullptr};  // per slot: recorded after the main walk grid (and wseed)
-  hipEvent_t ev_lagw[3] = {nullptr, nullptr, nullptr};
   int stream_prio = 1;
   int walk_cu_reserve = 0;  // option "walk_cu_reserve" k = 1..7: lag-2 walk streams kept off k/8 of the CUs
-  hipEvent_t ev_lag[3] = {nullptr, nullptr, nullptr};
   int stream_prio_applied = 0;  // the priority setting the current streams were created with
   bool side_prio_set = false;   // option "side_priority" made the side stream (apply_stream_prio keeps it)
   // clrrt_round_prefetch: declared next samples; pf_state 1 = their walk was launched (lists in the
-  // *2 buffers, merge pending), 2 = merged and swapped in for pf_samples
+  // set ls[1], merge pending), 2 = merged and swapped in for pf_samples
   std::vector<clrrt_sample> pf_next, pf_samples;
   int pf_state = 0;
   // Deferred samples (BATCH option "defer_steps" T > 0; see Carry in clrrt_kernels.hip): every rollout chain
@@ -369,6 +392,9 @@ struct clrrt_ctx {
   // option "fail_after_exchange" k (fault injection, tests): the k-th exchange from now fails after the hook
   // returned (as a failure of the work that follows the round's exchange would)
   int fail_after_exchange = 0;
+  // option "fail_in_round" k (fault injection, tests): the k-th round from now fails with CLRRT_ECAPACITY in the
+  // driver's round body right after its commit, as a HIP error of the work queued there would (a host-side return)
+  int fail_in_round = 0;
   // CLRRT_DEBUG_SYNC (diagnostics, read once at clrrt_create): a heartbeat buffer the rollout kernel's waves
   // write, polled while waiting for the launch
   bool debug_sync = false;
@@ -381,7 +407,6 @@ struct clrrt_ctx {
   std::vector<clrrt_iteration> iters;
   std::vector<SampleOut> iter_tmp;
   // host staging (pinned)
-  clrrt_sample* h_samples = nullptr;
   int64_t* h_totals = nullptr;
   int* h_int = nullptr;
   // last round_eval bookkeeping
@@ -638,17 +663,27 @@ int clrrt_draw_samples(const clrrt_params* p, clrrt_rng* rng, int32_t n, clrrt_s
 
 const char* clrrt_last_error(const clrrt_ctx* c) { return c ? c->err.c_str() : "null context"; }
 
+// The six buffers of a list set for batches of B samples.
+static hipError_t alloc_lists(ListSet& s, int64_t B) {
+  hipError_t e = dalloc(&s.d_samples, B);
+  if (e == hipSuccess) e = hipHostMalloc((void**)&s.h_samples, sizeof(clrrt_sample) * B, hipHostMallocDefault);
+  if (e == hipSuccess) e = dalloc(&s.cand, B * CAND_K);
+  if (e == hipSuccess) e = dalloc(&s.ckey, B * CAND_K);
+  if (e == hipSuccess) e = dalloc(&s.ncand, B);
+  if (e == hipSuccess) e = dalloc(&s.ctie, B);
+  return e;
+}
+
 static void free_all(clrrt_ctx* c) {
-  if (c->side) hipStreamSynchronize(c->side);  // side-stream work (prefetched search) uses the *2 buffers
-  void* ptrs[] = {c->tree, c->nn, c->arena, c->obs, c->d_samples, c->pk, c->pi, c->cand, c->ckey, c->ncand,
-                  c->ctie, c->sort_scratch, c->res_spec, c->regnodes, c->res_gb, c->gbnodes, c->so, c->first_conflict,
+  if (c->side) hipStreamSynchronize(c->side);  // side-stream work (prefetched search) uses a list set
+  void* ptrs[] = {c->tree, c->nn, c->arena, c->obs, c->pk, c->pi, c->sort_scratch, c->res_spec, c->regnodes,
+                  c->res_gb, c->gbnodes, c->so, c->first_conflict,
                   c->out_nodes, c->jobs, c->slots, c->rep_buf, c->totals, c->work_ctr, c->grid_buf, c->occ_buf,
                   c->nn_seed, c->d_bbox, c->roll_q, c->roll_best, c->roll_perm, c->roll_pflag,
                   c->goal_recs, c->bp_path, c->path_nodes, c->path_rows, c->ri_int, c->ri_off, c->ri_cost,
                   c->ri_terms, c->nnw.keys, c->nnw.keys2, c->nnw.vals, c->nnw.vals2, c->nnw.tmp, c->nnw.P, c->nnw.Q,
                   c->nnw.CE, c->nnw.ID, c->nnw.tiles, c->nnw.supers, c->nnw.sorder, c->nnw.HEAD, c->nnw.ovf_n, c->nnw.ovf, c->nnw.pk, c->nnw.pi, c->nnw_alt.keys, c->nnw_alt.keys2, c->nnw_alt.vals, c->nnw_alt.vals2, c->nnw_alt.tmp, c->nnw_alt.P, c->nnw_alt.Q, c->nnw_alt.CE, c->nnw_alt.ID, c->nnw_alt.tiles, c->nnw_alt.supers, c->nnw_alt.sorder, c->nnw_alt.HEAD, c->nnw_alt.ovf_n, c->nnw_alt.ovf, c->nnw_alt.pk, c->nnw_alt.pi, c->nnw.skeys, c->nnw.sids, c->nnw_alt.skeys, c->nnw_alt.sids, c->cmp.packed, c->cmp.scanned,
-                  c->cmp.tmp, c->d_samples2, c->cand2, c->ckey2, c->ncand2, c->ctie2, c->d_samples3, c->cand3, c->ckey3,
-                  c->ncand3, c->ctie3, c->nnw3.keys, c->nnw3.keys2, c->nnw3.vals, c->nnw3.vals2, c->nnw3.tmp, c->nnw3.P,
+                  c->cmp.tmp, c->nnw3.keys, c->nnw3.keys2, c->nnw3.vals, c->nnw3.vals2, c->nnw3.tmp, c->nnw3.P,
                   c->nnw3.Q, c->nnw3.CE, c->nnw3.ID, c->nnw3.tiles, c->nnw3.supers, c->nnw3.sorder, c->nnw3.HEAD,
                   c->nnw3.ovf_n, c->nnw3.ovf, c->nnw3.pk, c->nnw3.pi, c->nnw3.skeys, c->nnw3.sids,
                   c->nnw.trun, c->nnw_alt.trun, c->nnw3.trun, c->nnw.wctr, c->nnw_alt.wctr, c->nnw3.wctr};
@@ -665,22 +700,18 @@ static void free_all(clrrt_ctx* c) {
     if (p) hipFree(p);
   for (auto e : c->occ_ev)
     if (e) hipEventDestroy(e);
-  if (c->h_samples) hipHostFree(c->h_samples);
-  if (c->h_samples2) hipHostFree(c->h_samples2);
-  if (c->h_samples3) hipHostFree(c->h_samples3);
   if (c->side2) hipStreamSynchronize(c->side2);
   if (c->side2) hipStreamDestroy(c->side2);
-  for (auto e : c->ev_lag)
-    if (e) hipEventDestroy(e);
-  for (auto e : c->ev_lagw)
-    if (e) hipEventDestroy(e);
   if (c->mst) hipStreamSynchronize(c->mst);
   if (c->mst) hipStreamDestroy(c->mst);
-  for (int q = 0; q < 3; q++) {
-    if (c->wseed[q]) hipFree(c->wseed[q]);
-    if (q == 0 && c->nn_order) hipFree(c->nn_order);
-    if (c->ev_wm[q]) hipEventDestroy(c->ev_wm[q]);
+  for (ListSet& s : c->sets) {  // the storage, whatever roles ls[] gives the sets
+    for (void* p : {(void*)s.d_samples, (void*)s.cand, (void*)s.ckey, (void*)s.ncand, (void*)s.ctie, (void*)s.wseed})
+      if (p) hipFree(p);
+    if (s.h_samples) hipHostFree(s.h_samples);
+    for (hipEvent_t e : {s.ev, s.evw, s.evm})
+      if (e) hipEventDestroy(e);
   }
+  if (c->nn_order) hipFree(c->nn_order);
   {
     WalkBufs& d = c->nnw_d;
     void* wd[] = {d.keys, d.vals, d.tmp, d.P, d.Q, d.CE, d.ID, d.HEAD, d.trun, d.tiles, d.supers, d.skeys, d.sids,
@@ -746,19 +777,10 @@ int clrrt_create(const clrrt_params* p, const clrrt_capacity* cap, int device, c
   chk(dalloc(&c->nn, c->cap.max_nodes));
   chk(dalloc(&c->arena, (size_t)c->cap.max_rows * 10));
   chk(dalloc(&c->obs, std::max<int64_t>(1, c->cap.max_obstacles)));
-  chk(dalloc(&c->d_samples, B));
+  for (int q = 0; q < 2; q++) chk(alloc_lists(c->sets[q], B));
   c->partial_cap = std::max<int64_t>(B * 16, 4096) * NN_K;
   chk(dalloc(&c->pk, c->partial_cap));
   chk(dalloc(&c->pi, c->partial_cap));
-  chk(dalloc(&c->cand, B * CAND_K));
-  chk(dalloc(&c->ckey, B * CAND_K));
-  chk(dalloc(&c->ncand, B));
-  chk(dalloc(&c->ctie, B));
-  chk(dalloc(&c->d_samples2, B));
-  chk(dalloc(&c->cand2, B * CAND_K));
-  chk(dalloc(&c->ckey2, B * CAND_K));
-  chk(dalloc(&c->ncand2, B));
-  chk(dalloc(&c->ctie2, B));
   chk(hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking));
   chk(hipEventCreateWithFlags(&c->ev_tree, hipEventDisableTiming));
   chk(hipEventCreateWithFlags(&c->ev_walk, hipEventDisableTiming));
@@ -792,8 +814,6 @@ int clrrt_create(const clrrt_params* p, const clrrt_capacity* cap, int device, c
   chk(hipHostMalloc((void**)&c->h_bbox, sizeof(double) * 4, hipHostMallocDefault));
   chk(dalloc(&c->work_ctr, 64));
   if (rc == CLRRT_OK) chk(hipMemset(c->work_ctr, 0, 64 * sizeof(unsigned long long)));
-  chk(hipHostMalloc((void**)&c->h_samples, sizeof(clrrt_sample) * B, hipHostMallocDefault));
-  chk(hipHostMalloc((void**)&c->h_samples2, sizeof(clrrt_sample) * B, hipHostMallocDefault));
   chk(hipHostMalloc((void**)&c->h_totals, sizeof(int64_t) * 8, hipHostMallocDefault));
   chk(hipHostMalloc((void**)&c->h_int, sizeof(int) * 4, hipHostMallocDefault));
   if (rc != CLRRT_OK) {
@@ -1615,6 +1635,7 @@ int clrrt_set_option(clrrt_ctx* c, const char* key, int64_t value) {
   else if (k == "nn_debug" && value >= 0) c->nn_debug = (int)value;  // diagnostics: changes results
   else if (k == "fail_at_round" && value >= 0 && value < INT_MAX) c->fail_at_round = (int)value;  // fault injection
   else if (k == "fail_after_exchange" && value >= 0 && value < INT_MAX) c->fail_after_exchange = (int)value;
+  else if (k == "fail_in_round" && value >= 0 && value < INT_MAX) c->fail_in_round = (int)value;
   else if (k == "shard_hook_world1") c->sh.hook_world1 = value != 0;  // read by the next clrrt_set_shards
   else if (k == "roll_blocks" && value >= 0 && value < (1 << 20)) c->roll_blocks = (int)value;
   else if (k == "nn_pipeline") c->nn_pipeline = value != 0;
@@ -1703,10 +1724,11 @@ int clrrt_kernel_time(clrrt_ctx* c, int32_t which, double* ms, int64_t* launches
 static RollArgs roll_args(clrrt_ctx* c, int njobs) {
   RollArgs a;
   memset(&a, 0, sizeof(a));
+  ListSet& cur = *c->ls[0];
   a.p = c->dp;
   a.tree = c->tree;
-  a.samples = c->d_samples;
-  a.cand = c->cand;
+  a.samples = cur.d_samples;
+  a.cand = cur.cand;
   a.jobs = c->jobs;
   a.obs = c->obs;
   a.arena = c->arena;
@@ -1791,12 +1813,6 @@ static int ensure_walk_set(clrrt_ctx* c, WalkBufs& w) {
 }
 static int ensure_walk(clrrt_ctx* c) { return ensure_walk_set(c, c->nnw); }
 
-// Search region (the sampling region and the tree's box) and the float frame of the searches.
-struct NnSetup {
-  NnFrame fr;
-  double x0, y0, x1, y1;
-  bool region_ok;
-};
 static NnSetup nn_setup(clrrt_ctx* c) {
   NnSetup su;
   double& x0 = su.x0; double& y0 = su.y0; double& x1 = su.x1; double& y1 = su.y1;
@@ -1844,26 +1860,23 @@ static void pf_reset(clrrt_ctx* c) {
   c->nnw3.sorted_n = -1;
 }
 
-// Launches the walk search of samples h2[0..n2) (host, pinned) over the current tree on the side
-// stream into the *2 buffers; eval_samples records ev_tree before its rollouts.
+// The pipelined rounds' indexes cover the whole tree as it is now, under the current index options.
+static bool tree_index_matches(const clrrt_ctx* c, const BuiltFor& b, const NnSetup& su) {
+  return b.matches(c->n_nodes, 0, c->n_nodes, su, c->nnw_index, c->nnw_hscale);
+}
+static void tree_index_set(const clrrt_ctx* c, BuiltFor& b, const NnSetup& su) {
+  b.set(c->n_nodes, 0, c->n_nodes, su, c->nnw_index, c->nnw_hscale);
+}
 // The index is built on the main stream before the rollouts (its radix sort's look-back passes starve
 // beside the rollout kernel on large trees: 3+ ms instead of 0.2), the search runs on the side stream.
-static bool walk_built_for(const clrrt_ctx* c, const NnSetup& su) {
-  const auto& b = c->nnw_built;
-  return b.n == c->n_nodes && b.ox == su.fr.ox && b.oy == su.fr.oy && b.delta == su.fr.delta && b.x0 == su.x0 &&
-         b.y0 == su.y0 && b.x1 == su.x1 && b.y1 == su.y1;
-}
 static int pre_roll_build(clrrt_ctx* c, const NnSetup& su) {
   KTimer kt(c, 0, c->stream);
   const int rw = ensure_walk(c);
   if (rw != CLRRT_OK) return rw;
-  if (walk_built_for(c, su)) return CLRRT_OK;  // built ahead (next_round_build)
+  if (tree_index_matches(c, c->nnw_built, su)) return CLRRT_OK;  // built ahead (next_round_build)
   HIPC(c, launch_nn_walk_build(c->stream, c->nn, (int)c->n_nodes, su.fr, su.x0, su.y0, su.x1, su.y1, c->nnw,
                                c->nnw_alt.P ? &c->nnw_alt : nullptr));
-  auto& b = c->nnw_built;
-  b.n = c->n_nodes;
-  b.ox = su.fr.ox; b.oy = su.fr.oy; b.delta = su.fr.delta;
-  b.x0 = su.x0; b.y0 = su.y0; b.x1 = su.x1; b.y1 = su.y1;
+  tree_index_set(c, c->nnw_built, su);
   return CLRRT_OK;
 }
 
@@ -1878,16 +1891,19 @@ static int next_round_build(clrrt_ctx* c) {
   return pre_roll_build(c, su);
 }
 
+// Launches the walk search of the n2 samples in ls[1]'s host copy over the current tree on the side
+// stream into that set; eval_samples records ev_tree before its rollouts.
 static int launch_side_walk(clrrt_ctx* c, int n2, const NnSetup& su) {
+  ListSet& nxt = *c->ls[1];
   c->nn_bf_keys += (int64_t)n2 * c->n_nodes;
   c->nn_samples += n2;
   HIPC(c, hipStreamWaitEvent(c->side, c->ev_tree, 0));
-  HIPC(c, hipMemcpyAsync(c->d_samples2, c->h_samples2, sizeof(clrrt_sample) * n2, hipMemcpyHostToDevice, c->side));
+  HIPC(c, hipMemcpyAsync(nxt.d_samples, nxt.h_samples, sizeof(clrrt_sample) * n2, hipMemcpyHostToDevice, c->side));
   c->nn_super_bounds += (int64_t)n2 * walk_super_count(c->n_nodes);
   {
     KTimer kt(c, 0, c->side), kt3(c, 3, c->side);
-    HIPC(c, launch_nn_walk_search(c->side, c->d_samples2, n2, c->nn, (int)c->n_nodes, c->dp, su.fr, su.x0, su.y0,
-                                  su.x1, su.y1, c->nnw, c->cand2, c->ckey2, c->ncand2, c->ctie2, c->work_ctr + 18,
+    HIPC(c, launch_nn_walk_search(c->side, nxt.d_samples, n2, c->nn, (int)c->n_nodes, c->dp, su.fr, su.x0, su.y0,
+                                  su.x1, su.y1, c->nnw, nxt.cand, nxt.ckey, nxt.ncand, nxt.ctie, c->work_ctr + 18,
                                   c->nnw_stateless));
   }
   HIPC(c, hipEventRecord(c->ev_walk, c->side));
@@ -1899,6 +1915,7 @@ static int launch_side_walk(clrrt_ctx* c, int n2, const NnSetup& su) {
 // stream behind the walk, so the main stream can build the next round's index meanwhile.
 static int side_delta_launch(clrrt_ctx* c, int n2, int64_t first_new, int nn) {
   if (nn <= 0) return CLRRT_OK;
+  ListSet& nxt = *c->ls[1];
   HIPC(c, hipEventRecord(c->ev_commit, c->stream));
   HIPC(c, hipStreamWaitEvent(c->side, c->ev_commit, 0));
   {
@@ -1906,25 +1923,20 @@ static int side_delta_launch(clrrt_ctx* c, int n2, int64_t first_new, int nn) {
     c->nn_bf_keys += (int64_t)n2 * nn;
     const NnSetup su2 = nn_setup(c);  // the box includes the appended nodes
     const int max_chunks = (int)std::max<int64_t>(1, c->partial_cap / ((int64_t)n2 * NN_K));
-    HIPC(c, launch_nn_delta(c->side, c->d_samples2, n2, c->nn, (int)first_new, nn, c->dp, su2.fr, c->pk, c->pi,
-                            max_chunks, c->cand2, c->ckey2, c->ncand2, c->ctie2, c->nn_seed));
+    HIPC(c, launch_nn_delta(c->side, nxt.d_samples, n2, c->nn, (int)first_new, nn, c->dp, su2.fr, c->pk, c->pi,
+                            max_chunks, nxt.cand, nxt.ckey, nxt.ncand, nxt.ctie, c->nn_seed));
   }
   HIPC(c, hipEventRecord(c->ev_walk, c->side));
   return CLRRT_OK;
 }
 
-// The main stream waits for the side stream's lists and swaps the *2 buffers in.
+// The main stream waits for the side stream's lists and their set becomes the current one.
 static int side_lists_join(clrrt_ctx* c) {
   {
     KTimer kt(c, 4);  // the lists' wait (time the main stream stalls on the side stream)
     HIPC(c, hipStreamWaitEvent(c->stream, c->ev_walk, 0));
   }
-  std::swap(c->d_samples, c->d_samples2);
-  std::swap(c->h_samples, c->h_samples2);
-  std::swap(c->cand, c->cand2);
-  std::swap(c->ckey, c->ckey2);
-  std::swap(c->ncand, c->ncand2);
-  std::swap(c->ctie, c->ctie2);
+  std::swap(c->ls[0], c->ls[1]);
   return CLRRT_OK;
 }
 
@@ -1933,16 +1945,17 @@ static int merge_side_lists(clrrt_ctx* c, int n2, int64_t first_new, int nn) {
   return rc != CLRRT_OK ? rc : side_lists_join(c);
 }
 
-// Stage 1: candidate lists of samples c->d_samples[0..n) (spatial index for large trees).
+// Stage 1: candidate lists of samples cur.d_samples[0..n) (spatial index for large trees).
 static int run_nn(clrrt_ctx* c, int n, KeyId* scratch) {
   hipStream_t st = c->stream;
+  ListSet& cur = *c->ls[0];
   KTimer kt(c, 0);
   c->nn_bf_keys += (int64_t)n * c->n_nodes;
   c->nn_samples += n;
   int max_chunks = (int)std::max<int64_t>(1, c->partial_cap / ((int64_t)n * NN_K));
   if (scratch && c->nn_exact_fused && c->n_nodes <= nn_exact_small_max()) {  // EXACT rounds on small trees
-    HIPC(c, launch_nn_exact_small(st, c->d_samples, n, c->nn, (int)c->n_nodes, c->dp, c->cand, c->ckey, c->ncand,
-                                  c->ctie));
+    HIPC(c, launch_nn_exact_small(st, cur.d_samples, n, c->nn, (int)c->n_nodes, c->dp, cur.cand, cur.ckey, cur.ncand,
+                                  cur.ctie));
     return CLRRT_OK;
   }
   const NnSetup su = nn_setup(c);
@@ -1950,14 +1963,14 @@ static int run_nn(clrrt_ctx* c, int n, KeyId* scratch) {
     int rc = ensure_walk(c);
     if (rc != CLRRT_OK) return rc;
     c->nnw_built.n = -1;
-    HIPC(c, launch_nn_walk(st, c->d_samples, n, c->nn, (int)c->n_nodes, c->dp, su.fr, su.x0, su.y0, su.x1, su.y1,
-                           c->nnw, c->cand, c->ckey, c->ncand, c->ctie, c->work_ctr + 18, c->nnw_stateless));
-    if (scratch) HIPC(c, launch_nn_exact_only(st, c->d_samples, n, c->nn, (int)c->n_nodes, c->dp, c->ctie, scratch,
-                                              c->cand, c->ckey, c->ncand));
+    HIPC(c, launch_nn_walk(st, cur.d_samples, n, c->nn, (int)c->n_nodes, c->dp, su.fr, su.x0, su.y0, su.x1, su.y1,
+                           c->nnw, cur.cand, cur.ckey, cur.ncand, cur.ctie, c->work_ctr + 18, c->nnw_stateless));
+    if (scratch) HIPC(c, launch_nn_exact_only(st, cur.d_samples, n, c->nn, (int)c->n_nodes, c->dp, cur.ctie, scratch,
+                                              cur.cand, cur.ckey, cur.ncand));
     return CLRRT_OK;
   }
-  HIPC(c, launch_nn(st, c->d_samples, n, c->nn, (int)c->n_nodes, c->dp, c->pk, c->pi, c->cand, c->ckey,
-                    c->ncand, c->ctie, max_chunks, scratch, c->nn_seed, c->work_ctr + 8, su.fr));
+  HIPC(c, launch_nn(st, cur.d_samples, n, c->nn, (int)c->n_nodes, c->dp, c->pk, c->pi, cur.cand, cur.ckey,
+                    cur.ncand, cur.ctie, max_chunks, scratch, c->nn_seed, c->work_ctr + 8, su.fr));
   return CLRRT_OK;
 }
 
@@ -1972,6 +1985,7 @@ static int run_nn(clrrt_ctx* c, int n, KeyId* scratch) {
 // list's tried candidates.  *L: the prefix.
 static int exact_fixups(clrrt_ctx* c, int n, int* L) {
   hipStream_t st = c->stream;
+  ListSet& cur = *c->ls[0];
   const int64_t B = c->cap.max_batch;
   const int K = CAND_K;
   if (!c->fix_n) {
@@ -1988,7 +2002,7 @@ static int exact_fixups(clrrt_ctx* c, int n, int* L) {
   }
   {
     KTimer kt(c, 2);
-    HIPC(c, launch_conflict_fix(st, c->dp, n, c->d_samples, c->regnodes, c->gbnodes, c->so, c->ctie, c->ncand, c->ckey,
+    HIPC(c, launch_conflict_fix(st, c->dp, n, cur.d_samples, c->regnodes, c->gbnodes, c->so, cur.ctie, cur.ncand, cur.ckey,
                                 c->res_spec, c->fix_n, c->fix_ids, c->fix_adj));
   }
   c->h_fix.resize((size_t)n * (1 + FIX_MAX + 5));
@@ -2000,9 +2014,9 @@ static int exact_fixups(clrrt_ctx* c, int n, int* L) {
   HIPC(c, hipMemcpyAsync(c->h_fix.data() + n, c->fix_ids, sizeof(int) * n * FIX_MAX, hipMemcpyDeviceToHost, st));
   HIPC(c, hipMemcpyAsync(c->h_fix.data() + n * (1 + FIX_MAX), c->fix_adj, sizeof(int) * n * 5, hipMemcpyDeviceToHost,
                          st));
-  HIPC(c, hipMemcpyAsync(c->h_fix_smp.data(), c->d_samples, sizeof(clrrt_sample) * n, hipMemcpyDeviceToHost, st));
+  HIPC(c, hipMemcpyAsync(c->h_fix_smp.data(), cur.d_samples, sizeof(clrrt_sample) * n, hipMemcpyDeviceToHost, st));
   HIPC(c, hipMemcpyAsync(c->h_fix_so.data(), c->so, sizeof(SampleOut) * n, hipMemcpyDeviceToHost, st));
-  HIPC(c, hipMemcpyAsync(c->h_fix_cand.data(), c->cand, sizeof(int) * n * K, hipMemcpyDeviceToHost, st));
+  HIPC(c, hipMemcpyAsync(c->h_fix_cand.data(), cur.cand, sizeof(int) * n * K, hipMemcpyDeviceToHost, st));
   HIPC(c, hipMemcpyAsync(c->h_fix_spec.data(), c->res_spec, sizeof(RollRes) * n * K, hipMemcpyDeviceToHost, st));
   HIPC(c, hipStreamSynchronize(st));
   const int* fn = c->h_fix.data();
@@ -2038,7 +2052,7 @@ static int exact_fixups(clrrt_ctx* c, int n, int* L) {
     HIPC(c, hipMemcpyAsync(c->fix_xi, xs.data(), sizeof(int) * 2 * nl, hipMemcpyHostToDevice, st));
     {
       KTimer kt(c, 0);
-      HIPC(c, launch_nn_exact_x(st, c->d_samples, c->nn, (int)N, c->dp, c->regnodes, c->gbnodes, c->so, n, c->fix_xrec,
+      HIPC(c, launch_nn_exact_x(st, cur.d_samples, c->nn, (int)N, c->dp, c->regnodes, c->gbnodes, c->so, n, c->fix_xrec,
                                 c->fix_xi, c->fix_xi + nl, nl, xpre[n], c->fix_xcand, c->fix_xkey, c->fix_xn,
                                 c->fix_xn + nl));
     }
@@ -2177,13 +2191,15 @@ static int exact_fixups(clrrt_ctx* c, int n, int* L) {
   return CLRRT_OK;
 }
 
-// Stages 1-4 (+5 in EXACT mode) for n samples already in c->d_samples.  Returns the number of
-// samples to commit (n in BATCH mode).  have_lists: the candidate lists are already in c->cand
+// Stages 1-4 (+5 in EXACT mode) for n samples already in cur.d_samples.  Returns the number of
+// samples to commit (n in BATCH mode).  have_lists: the candidate lists are already in cur.cand
 // (pipelined rounds); during_roll runs right after the rollout kernel's launch.
 static int eval_samples(clrrt_ctx* c, int n, bool exact, int* L_out, bool have_lists = false,
                         const std::function<int()>& during_roll = nullptr,
                         const std::function<int()>& pre_roll = nullptr) {
   hipStream_t st = c->stream;
+  ListSet& cur = *c->ls[0];
+  c->totals_zeroed = false;  // (a round that failed after its prologue fill leaves nothing behind)
   KeyId* scratch = nullptr;
   if (exact) {
     int rc = ensure_sort_scratch(c, (int64_t)n * c->n_nodes);
@@ -2221,10 +2237,10 @@ static int eval_samples(clrrt_ctx* c, int n, bool exact, int* L_out, bool have_l
     auto& d = c->def;
     d.slot = (int)(d.round % d.R);
     const int64_t B = c->cap.max_batch;
-    HIPC(c, hipMemcpyAsync(d.cand + (int64_t)d.slot * B * CAND_K, c->cand, sizeof(int) * n * CAND_K,
+    HIPC(c, hipMemcpyAsync(d.cand + (int64_t)d.slot * B * CAND_K, cur.cand, sizeof(int) * n * CAND_K,
                            hipMemcpyDeviceToDevice, st));
-    HIPC(c, hipMemcpyAsync(d.ncand + (int64_t)d.slot * B, c->ncand, sizeof(int) * n, hipMemcpyDeviceToDevice, st));
-    HIPC(c, hipMemcpyAsync(d.samp + (int64_t)d.slot * B, c->d_samples, sizeof(clrrt_sample) * n,
+    HIPC(c, hipMemcpyAsync(d.ncand + (int64_t)d.slot * B, cur.ncand, sizeof(int) * n, hipMemcpyDeviceToDevice, st));
+    HIPC(c, hipMemcpyAsync(d.samp + (int64_t)d.slot * B, cur.d_samples, sizeof(clrrt_sample) * n,
                            hipMemcpyDeviceToDevice, st));
     if (d.nd + (int64_t)n > d.vcap) return fail(c, CLRRT_ECAPACITY, "deferred samples exceed the commit buffers");
     if (rst != st) {  // the copies precede the rollouts' ring writes
@@ -2329,7 +2345,7 @@ static int eval_samples(clrrt_ctx* c, int n, bool exact, int* L_out, bool have_l
   }
   SelArgs s;
   memset(&s, 0, sizeof(s));
-  s.p = c->dp; s.tree = c->tree; s.cand = c->cand; s.ckey = c->ckey; s.ncand = c->ncand; s.res = c->res_spec;
+  s.p = c->dp; s.tree = c->tree; s.cand = cur.cand; s.ckey = cur.ckey; s.ncand = cur.ncand; s.res = c->res_spec;
   s.res_gb = c->res_gb; s.regnodes = c->regnodes; s.gbnodes = c->gbnodes; s.so = c->so; s.B = n;
   if (defer) {  // views: the deferred samples of earlier rounds, then this round's
     auto& d = c->def;
@@ -2357,7 +2373,7 @@ static int eval_samples(clrrt_ctx* c, int n, bool exact, int* L_out, bool have_l
     HIPC(c, hipMemcpyAsync(c->first_conflict, c->h_int, sizeof(int), hipMemcpyHostToDevice, st));
     {
       KTimer kt(c, 2);
-      HIPC(c, launch_conflict(st, c->dp, n, c->d_samples, c->regnodes, c->gbnodes, c->so, c->ctie,
+      HIPC(c, launch_conflict(st, c->dp, n, cur.d_samples, c->regnodes, c->gbnodes, c->so, cur.ctie,
                               c->first_conflict));
     }
     HIPC(c, hipMemcpyAsync(c->h_int + 1, c->first_conflict, sizeof(int), hipMemcpyDeviceToHost, st));
@@ -2372,13 +2388,14 @@ static int eval_samples(clrrt_ctx* c, int n, bool exact, int* L_out, bool have_l
 // copy the accepted trajectories into the arena.  *n_out = records.
 static int compact_and_copy(clrrt_ctx* c, int L, int* n_out, bool merge_bbox) {
   hipStream_t st = c->stream;
+  ListSet& cur = *c->ls[0];
   auto& d = c->def;
   const bool defer = d.nd_eval >= 0;  // eval_samples selected views (deferred samples + this round's)
   const int V = defer ? d.nd_eval + L : L;
   {
     KTimer kt(c, 2);
     const bool tag = defer && c->sh.fn;  // the exchange orders deferred samples by age
-    HIPC(c, launch_compact(st, V, c->d_samples, c->cand, c->regnodes, c->gbnodes, c->so, c->n_rows, c->rank,
+    HIPC(c, launch_compact(st, V, cur.d_samples, cur.cand, c->regnodes, c->gbnodes, c->so, c->n_rows, c->rank,
                            c->out_nodes, c->jobs, c->totals, c->cmp, tag ? d.slot : 0, tag ? d.R : 0,
                            (int)c->cap.max_batch, c->totals_zeroed));
     c->totals_zeroed = false;
@@ -2441,7 +2458,7 @@ static int compact_and_copy(clrrt_ctx* c, int L, int* n_out, bool merge_bbox) {
     if (defer)  // the committed samples' lists and results sit in the rings
       HIPC(c, launch_replay_gather(st, c->jobs, c->out_nodes, (int)nn, c->tree, d.cand, d.samp, d.res, c->rep_buf));
     else
-      HIPC(c, launch_replay_gather(st, c->jobs, c->out_nodes, (int)nn, c->tree, c->cand, c->d_samples, c->res_spec,
+      HIPC(c, launch_replay_gather(st, c->jobs, c->out_nodes, (int)nn, c->tree, cur.cand, cur.d_samples, c->res_spec,
                                    c->rep_buf));
     c->rep_n = (int)nn;
   } else {
@@ -2679,8 +2696,9 @@ int clrrt_round_eval(clrrt_ctx* c, const clrrt_sample* samples, int32_t n, void*
                     memcmp(c->pf_samples.data(), samples, sizeof(clrrt_sample) * n) == 0;
   if (!have) {
     if (c->pf_state != 0 && c->side) HIPC(c, hipStreamSynchronize(c->side));
-    memcpy(c->h_samples, samples, sizeof(clrrt_sample) * n);
-    HIPC(c, hipMemcpyAsync(c->d_samples, c->h_samples, sizeof(clrrt_sample) * n, hipMemcpyHostToDevice, c->stream));
+    ListSet& cur = *c->ls[0];
+    memcpy(cur.h_samples, samples, sizeof(clrrt_sample) * n);
+    HIPC(c, hipMemcpyAsync(cur.d_samples, cur.h_samples, sizeof(clrrt_sample) * n, hipMemcpyHostToDevice, c->stream));
   }
   c->pf_state = 0;
   const int n2 = (int)std::min<size_t>(c->pf_next.size(), (size_t)c->cap.max_batch);
@@ -2691,7 +2709,7 @@ int clrrt_round_eval(clrrt_ctx* c, const clrrt_sample* samples, int32_t n, void*
     side = walk_serves(c, su);
   }
   auto during = [&]() -> int {
-    memcpy(c->h_samples2, c->pf_next.data(), sizeof(clrrt_sample) * n2);
+    memcpy(c->ls[1]->h_samples, c->pf_next.data(), sizeof(clrrt_sample) * n2);
     c->pf_samples.assign(c->pf_next.begin(), c->pf_next.begin() + n2);
     c->pf_state = 1;
     return launch_side_walk(c, n2, su);
@@ -2754,18 +2772,12 @@ int clrrt_round_prefetch(clrrt_ctx* c, const clrrt_sample* next, int32_t n) {
 // Tree-partitioned search: a rank searches every sample of the round over its node range only (clrrt_nn_range), the
 // ranks' lists are merged in (key, id) order (clrrt_nn_merge) and the round's rollouts run from the merged lists
 // (clrrt_round_eval_lists).  The three use the context's list buffers (cand, ckey, ncand, ctie) on the main stream.
-static bool range_built_for(const clrrt_ctx* c, const NnSetup& su, int64_t first, int64_t count) {
-  const auto& b = c->nnr_built;
-  return b.n == c->n_nodes && b.first == first && b.count == count && b.ox == su.fr.ox && b.oy == su.fr.oy &&
-         b.delta == su.fr.delta && b.x0 == su.x0 && b.y0 == su.y0 && b.x1 == su.x1 && b.y1 == su.y1 &&
-         b.kind == c->nnw_index && b.hscale == c->nnw_hscale;
-}
-
 // The lists (cand, ckey, ncand) to the caller (host or device memory), after everything queued on the stream.
 static int lists_out(clrrt_ctx* c, int n, int32_t* out_ids, float* out_keys, int32_t* out_n) {
-  HIPC(c, hipMemcpyAsync(out_ids, c->cand, sizeof(int) * CAND_K * n, hipMemcpyDefault, c->stream));
-  HIPC(c, hipMemcpyAsync(out_keys, c->ckey, sizeof(float) * CAND_K * n, hipMemcpyDefault, c->stream));
-  HIPC(c, hipMemcpyAsync(out_n, c->ncand, sizeof(int) * n, hipMemcpyDefault, c->stream));
+  ListSet& cur = *c->ls[0];
+  HIPC(c, hipMemcpyAsync(out_ids, cur.cand, sizeof(int) * CAND_K * n, hipMemcpyDefault, c->stream));
+  HIPC(c, hipMemcpyAsync(out_keys, cur.ckey, sizeof(float) * CAND_K * n, hipMemcpyDefault, c->stream));
+  HIPC(c, hipMemcpyAsync(out_n, cur.ncand, sizeof(int) * n, hipMemcpyDefault, c->stream));
   HIPC(c, hipStreamSynchronize(c->stream));
   return CLRRT_OK;
 }
@@ -2780,43 +2792,40 @@ int clrrt_nn_range(clrrt_ctx* c, const clrrt_sample* samples, int32_t n, int64_t
   if (n > c->cap.max_batch) return fail(c, CLRRT_ECAPACITY, "batch larger than max_batch");
   if (n == 0) return CLRRT_OK;
   pf_discard(c);  // the list buffers are overwritten
+  ListSet& cur = *c->ls[0];
   HIPC(c, hipSetDevice(c->device));
   hipStream_t st = c->stream;
-  memcpy(c->h_samples, samples, sizeof(clrrt_sample) * n);
-  HIPC(c, hipMemcpyAsync(c->d_samples, c->h_samples, sizeof(clrrt_sample) * n, hipMemcpyHostToDevice, st));
+  memcpy(cur.h_samples, samples, sizeof(clrrt_sample) * n);
+  HIPC(c, hipMemcpyAsync(cur.d_samples, cur.h_samples, sizeof(clrrt_sample) * n, hipMemcpyHostToDevice, st));
   c->nn_bf_keys += (int64_t)n * count;
   c->nn_samples += n;
   {
     KTimer kt(c, 0);
-    HIPC(c, hipMemsetAsync(c->ncand, 0, sizeof(int) * n, st));  // count == 0, and the brute force's empty older list
+    HIPC(c, hipMemsetAsync(cur.ncand, 0, sizeof(int) * n, st));  // count == 0, and the brute force's empty older list
     const NnSetup su = nn_setup(c);  // the whole tree's frame: the same on every rank
     if (count > 0 && count >= c->nnw_min_nodes && su.region_ok) {
       WalkBufs& w = c->nnw_r;
       const int rc = ensure_walk_set(c, w);
       if (rc != CLRRT_OK) return rc;
-      if (!range_built_for(c, su, first, count)) {
+      if (!c->nnr_built.matches(c->n_nodes, first, count, su, c->nnw_index, c->nnw_hscale)) {
         c->nnr_built.n = -1;
         HIPC(c, launch_nn_walk_build(st, c->nn, (int)count, su.fr, su.x0, su.y0, su.x1, su.y1, w, nullptr, (int)first));
-        auto& b = c->nnr_built;
-        b.n = c->n_nodes; b.first = first; b.count = count;
-        b.ox = su.fr.ox; b.oy = su.fr.oy; b.delta = su.fr.delta;
-        b.x0 = su.x0; b.y0 = su.y0; b.x1 = su.x1; b.y1 = su.y1;
-        b.kind = c->nnw_index; b.hscale = c->nnw_hscale;
+        c->nnr_built.set(c->n_nodes, first, count, su, c->nnw_index, c->nnw_hscale);
       }
       c->nn_super_bounds += (int64_t)n * walk_super_count(count);
       KTimer kt3(c, 3);
-      HIPC(c, launch_nn_walk_search(st, c->d_samples, n, c->nn, (int)count, c->dp, su.fr, su.x0, su.y0, su.x1, su.y1, w,
-                                    c->cand, c->ckey, c->ncand, c->ctie, c->work_ctr + 18, c->nnw_stateless));
+      HIPC(c, launch_nn_walk_search(st, cur.d_samples, n, c->nn, (int)count, c->dp, su.fr, su.x0, su.y0, su.x1, su.y1, w,
+                                    cur.cand, cur.ckey, cur.ncand, cur.ctie, c->work_ctr + 18, c->nnw_stateless));
     } else if (count > 0) {
       // short ranges (and trees the walk does not serve): the brute force's chunk lists over the range, caps from
       // +inf, merged into the empty list
       const int max_chunks = (int)std::max<int64_t>(1, c->partial_cap / ((int64_t)n * NN_K));
       int nch = 0;
-      HIPC(c, launch_nn_delta_partial(st, c->d_samples, n, c->nn, (int)first, (int)count, c->dp, su.fr, c->pk, c->pi,
+      HIPC(c, launch_nn_delta_partial(st, cur.d_samples, n, c->nn, (int)first, (int)count, c->dp, su.fr, c->pk, c->pi,
                                       max_chunks, nullptr, nullptr, c->nn_seed, false, nullptr, &nch, c->work_ctr + 13));
-      HIPC(c, launch_nn_delta_merge(st, n, nch, c->dp, c->pk, c->pi, (int)first, c->cand, c->ckey, c->ncand, c->ctie));
+      HIPC(c, launch_nn_delta_merge(st, n, nch, c->dp, c->pk, c->pi, (int)first, cur.cand, cur.ckey, cur.ncand, cur.ctie));
     }
-    HIPC(c, launch_nn_lists_check(st, n, c->dp, (int)c->n_nodes, c->cand, c->ckey, c->ncand, c->ctie, nullptr));
+    HIPC(c, launch_nn_lists_check(st, n, c->dp, (int)c->n_nodes, cur.cand, cur.ckey, cur.ncand, cur.ctie, nullptr));
   }
   return lists_out(c, n, out_ids, out_keys, out_n);
 }
@@ -2828,6 +2837,7 @@ int clrrt_nn_merge(clrrt_ctx* c, int32_t n, int32_t parts, const int32_t* ids, c
   if (n > c->cap.max_batch) return fail(c, CLRRT_ECAPACITY, "batch larger than max_batch");
   if (n == 0) return CLRRT_OK;
   pf_discard(c);  // the list buffers are overwritten
+  ListSet& cur = *c->ls[0];
   HIPC(c, hipSetDevice(c->device));
   hipStream_t st = c->stream;
   const int64_t pairs = (int64_t)parts * n;
@@ -2847,8 +2857,8 @@ int clrrt_nn_merge(clrrt_ctx* c, int32_t n, int32_t parts, const int32_t* ids, c
   HIPC(c, hipMemcpyAsync(c->pm_counts, counts, sizeof(int) * pairs, hipMemcpyDefault, st));
   {
     KTimer kt(c, 0);
-    HIPC(c, launch_nn_merge_parts(st, n, parts, c->dp, c->pm_ids, c->pm_keys, c->pm_counts, c->cand, c->ckey, c->ncand,
-                                  c->ctie));
+    HIPC(c, launch_nn_merge_parts(st, n, parts, c->dp, c->pm_ids, c->pm_keys, c->pm_counts, cur.cand, cur.ckey, cur.ncand,
+                                  cur.ctie));
   }
   return lists_out(c, n, out_ids, out_keys, out_n);
 }
@@ -2862,18 +2872,19 @@ int clrrt_round_eval_lists(clrrt_ctx* c, const clrrt_sample* samples, int32_t n,
   *n_out = 0;
   if (n == 0) return CLRRT_OK;
   pf_discard(c);  // a prefetched search is for the engine's own lists
+  ListSet& cur = *c->ls[0];
   hipStream_t st = c->stream;
   if (!c->d_bad) HIPC(c, dalloc(&c->d_bad, 1));
-  memcpy(c->h_samples, samples, sizeof(clrrt_sample) * n);
-  HIPC(c, hipMemcpyAsync(c->d_samples, c->h_samples, sizeof(clrrt_sample) * n, hipMemcpyHostToDevice, st));
-  HIPC(c, hipMemcpyAsync(c->cand, ids, sizeof(int) * CAND_K * n, hipMemcpyDefault, st));
-  HIPC(c, hipMemcpyAsync(c->ckey, keys, sizeof(float) * CAND_K * n, hipMemcpyDefault, st));
-  HIPC(c, hipMemcpyAsync(c->ncand, counts, sizeof(int) * n, hipMemcpyDefault, st));
+  memcpy(cur.h_samples, samples, sizeof(clrrt_sample) * n);
+  HIPC(c, hipMemcpyAsync(cur.d_samples, cur.h_samples, sizeof(clrrt_sample) * n, hipMemcpyHostToDevice, st));
+  HIPC(c, hipMemcpyAsync(cur.cand, ids, sizeof(int) * CAND_K * n, hipMemcpyDefault, st));
+  HIPC(c, hipMemcpyAsync(cur.ckey, keys, sizeof(float) * CAND_K * n, hipMemcpyDefault, st));
+  HIPC(c, hipMemcpyAsync(cur.ncand, counts, sizeof(int) * n, hipMemcpyDefault, st));
   // the lists are checked on the device before any rollout reads them: counts in [0, sort_limit], listed ids inside
   // the tree (slots past the count become -1, which the rollouts skip)
   c->h_int[2] = 0x7fffffff;
   HIPC(c, hipMemcpyAsync(c->d_bad, c->h_int + 2, sizeof(int), hipMemcpyHostToDevice, st));
-  HIPC(c, launch_nn_lists_check(st, n, c->dp, (int)c->n_nodes, c->cand, c->ckey, c->ncand, c->ctie, c->d_bad));
+  HIPC(c, launch_nn_lists_check(st, n, c->dp, (int)c->n_nodes, cur.cand, cur.ckey, cur.ncand, cur.ctie, c->d_bad));
   HIPC(c, hipMemcpyAsync(c->h_int + 3, c->d_bad, sizeof(int), hipMemcpyDeviceToHost, st));
   HIPC(c, hipStreamSynchronize(st));
   if (c->h_int[3] != 0x7fffffff)
@@ -3033,34 +3044,21 @@ static int commit_round(clrrt_ctx* c, int nn, double elapsed_ms, int* n_app) {
 // searched by round r+1's walk, the one by round r+2's, the one being built for the next), and two side
 // streams (round r+1's merge must not wait behind round r+2's walk).  Results are those of plain rounds.
 struct LagSlot {
-  clrrt_sample* d = nullptr;
-  clrrt_sample* h = nullptr;
-  int* cand = nullptr;
-  float* ckey = nullptr;
-  int* ncand = nullptr;
-  int* ctie = nullptr;
-  hipEvent_t ev = nullptr;  // recorded after its merge
-  hipEvent_t evw = nullptr; // recorded after its walk (the merge waits for it on the merge stream)
-  int n = 0;                // samples searched (0: none): this rank's slice
-  int64_t g = 0;            // samples of the round (all ranks)
-  int64_t tree_n = 0;       // size of the tree its walk searched
-  int stream = 0;           // side stream index
-  // nn_delta_early: the appended-node search's caps taken after the walk's main grid, and the event recorded there
-  float* wseed = nullptr;
-  hipEvent_t evm = nullptr;
+  ListSet* set = nullptr;  // its list set (ls[1] for slot A, ls[2] for slot B)
+  int n = 0;               // samples searched (0: none): this rank's slice
+  int64_t g = 0;           // samples of the round (all ranks)
+  int64_t tree_n = 0;      // size of the tree its walk searched
+  int stream = 0;          // side stream index
 };
 
 static int lag_alloc(clrrt_ctx* c) {
   if (c->side2) return CLRRT_OK;
   const int64_t B = c->cap.max_batch;
-  HIPC(c, dalloc(&c->d_samples3, B));
-  HIPC(c, dalloc(&c->cand3, B * CAND_K));
-  HIPC(c, dalloc(&c->ckey3, B * CAND_K));
-  HIPC(c, dalloc(&c->ncand3, B));
-  HIPC(c, dalloc(&c->ctie3, B));
-  HIPC(c, hipHostMalloc((void**)&c->h_samples3, sizeof(clrrt_sample) * B, hipHostMallocDefault));
-  for (auto& e : c->ev_lag) HIPC(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  for (auto& e : c->ev_lagw) HIPC(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  HIPC(c, alloc_lists(c->sets[2], B));
+  for (ListSet& s : c->sets) {
+    for (hipEvent_t* e : {&s.ev, &s.evw, &s.evm}) HIPC(c, hipEventCreateWithFlags(e, hipEventDisableTiming));
+    HIPC(c, dalloc(&s.wseed, B));
+  }
   if (c->cu_split > 0) {  // the same CUs as the side stream
     const int nw = (c->n_cu + 31) / 32;
     std::vector<uint32_t> ms(nw, 0u);
@@ -3071,11 +3069,7 @@ static int lag_alloc(clrrt_ctx* c) {
     HIPC(c, hipStreamCreateWithFlags(&c->side2, hipStreamNonBlocking));
   }
   HIPC(c, hipStreamCreateWithFlags(&c->mst, hipStreamNonBlocking));
-  for (int q = 0; q < 3; q++) {
-    HIPC(c, dalloc(&c->wseed[q], B));
-    if (q == 0) HIPC(c, dalloc(&c->nn_order, B));
-    HIPC(c, hipEventCreateWithFlags(&c->ev_wm[q], hipEventDisableTiming));
-  }
+  HIPC(c, dalloc(&c->nn_order, B));
   return CLRRT_OK;
 }
 
@@ -3149,74 +3143,150 @@ static int apply_stream_prio(clrrt_ctx* c) {
   return CLRRT_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// The skeleton of an expansion, shared by its two drivers (clrrt_expand: EXACT and lag-1 BATCH rounds; expand_lag2):
+//   ExpandRun x(...);  rc = expand_begin(x, batch);
+//   while (rc == CLRRT_OK && round_plan(x, ...)) rc = <the driver's round body>;
+//   return expand_end(x, rc, rng, out);
+// Nothing returns between expand_begin and expand_end: a round body's failure (every HIPC in it) comes back as
+// its status, and the epilogue -- sharded, the closing exchange the other ranks wait in -- runs on every path.
+struct ExpandRun {
+  clrrt_ctx* c;
+  int64_t n_iters;
+  double budget_ms;
+  bool sharded;
+  clrrt_stats st{};
+  std::chrono::steady_clock::time_point t0, tr0;  // the expansion's start, the current round's
+  double ms0 = 0;                                 // query time at the current round's start
+  clrrt_rng work;       // draws ahead (speculative samples)
+  clrrt_rng committed;  // state after exactly `iterations` iterations
+  std::deque<clrrt_sample> pending;
+  int64_t nodes_before;
+  double last_round_ms = 0;
+  ExpandRun(clrrt_ctx* c_, const clrrt_rng& rng, int64_t n_iters_, double budget_ms_)
+      : c(c_), n_iters(n_iters_), budget_ms(budget_ms_), sharded(c_->sh.fn != nullptr),
+        t0(std::chrono::steady_clock::now()), tr0(t0), work(rng), committed(rng), nodes_before(c_->n_nodes) {}
+  double ms_since(std::chrono::steady_clock::time_point t) const {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
+  }
+};
+
+// The status goes into the driver's loop condition, never out of the driver.
+static int expand_begin(ExpandRun& x, bool batch) {
+  clrrt_ctx* c = x.c;
+  c->sh.max_ms = 0;
+  c->sh.nd_global = 0;
+  c->sh.rows_stop = 0;
+  c->totals_zeroed = false;
+  shard_expansion_begin(c);
+  int rc = defer_begin(c, batch);
+  if (rc == CLRRT_OK && x.sharded) rc = shard_goal_reset(c);
+  return rc;
+}
+
+static void draw_to(ExpandRun& x, int64_t want) {
+  while ((int64_t)x.pending.size() < want) {
+    clrrt_sample smp;
+    clrrt_draw_samples(&x.c->params, &x.work, 1, &smp);
+    x.pending.push_back(smp);
+  }
+}
+
+// Whether another round of up to `cur` samples runs: false when the iterations or the budget are used up, and when
+// the capacity cannot take the round -- st.capacity_stop for a budget query, *rc = CLRRT_ECAPACITY for an iteration
+// count.  *gb: the round's samples over all ranks; this rank's slice is [*f0, *f0 + *nb).
+static bool round_plan(ExpandRun& x, int64_t cur, int* rc, int64_t* gb, int64_t* f0, int* nb) {
+  clrrt_ctx* c = x.c;
+  x.tr0 = std::chrono::steady_clock::now();
+  if (x.n_iters > 0 && x.st.iterations >= x.n_iters) return false;
+  x.ms0 = std::chrono::duration<double, std::milli>(x.tr0 - x.t0).count();
+  // sharded: every rank decides on the largest elapsed time over the ranks (the same rounds everywhere)
+  if (x.n_iters == 0 && !((x.sharded ? c->sh.max_ms : x.ms0) < x.budget_ms)) return false;
+  *gb = x.n_iters > 0 ? std::min<int64_t>(cur, x.n_iters - x.st.iterations) : cur;
+  *f0 = 0;
+  *nb = (int)*gb;
+  if (x.sharded) shard_slice(c, *gb, f0, nb);
+  c->sh.last_nb = *nb;
+  // a round appends at most 2 nodes and 2 full-horizon trajectories per sample (+ the deferred samples that
+  // resolve; sharded, the same decision on every rank: node counts only, deferred samples bounded by the ring)
+  const int64_t nc = *gb + (x.sharded ? c->sh.nd_global : (int64_t)c->def.nd);
+  if (c->n_nodes + 2 * nc > c->cap.max_nodes ||
+      (x.sharded ? c->sh.rows_stop > 0 : c->n_rows + 2 * nc * (c->dp.n_steps_max + 1) > c->cap.max_rows)) {
+    if (x.n_iters > 0) *rc = fail(c, CLRRT_ECAPACITY, "tree capacity exhausted");
+    else x.st.capacity_stop = 1;
+    return false;
+  }
+  return true;
+}
+
+// A committed round: `used` iterations consumed (three draws each), `speculated` samples evaluated.
+static void round_done(ExpandRun& x, int64_t used, int64_t speculated) {
+  for (int64_t j = 0; j < used; j++) {
+    x.pending.pop_front();
+    for (int q = 0; q < 3; q++) clrrt_rng_next(&x.committed);
+  }
+  x.st.iterations += used;
+  x.st.goal_nodes_added += x.c->last_goal_nodes;
+  x.st.speculated += speculated;
+  x.st.rounds++;
+  x.last_round_ms = x.ms_since(x.tr0);
+}
+
+// The end of an expansion, on every path out of its rounds.
+static int expand_end(ExpandRun& x, int rc, clrrt_rng* rng, clrrt_stats* out) {
+  clrrt_ctx* c = x.c;
+  // the deferred samples still pending (sharded: an exchange the other ranks expect) and the last round's accepted
+  // rows: part of the query's output tree, so inside its time
+  if (rc == CLRRT_OK) rc = defer_drain(c, &x.st.goal_nodes_added);
+  x.st.deferred = c->def.deferred_total;
+  if (rc == CLRRT_OK) rc = flush_replays(c);
+  if (rc == CLRRT_OK && x.sharded) rc = shard_goal_count(c, &x.st.goal_nodes_added);
+  // every stream drained, the first error kept: before the closing exchange, so a late asynchronous error travels in it
+  for (hipStream_t s : {c->side, c->side2, c->mst, c->stream}) {
+    const hipError_t e = s ? hipStreamSynchronize(s) : hipSuccess;
+    if (e != hipSuccess && rc == CLRRT_OK)
+      rc = fail(c, CLRRT_EHIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(e));
+  }
+  rc = shard_expansion_end(c, rc);  // the closing exchange (sharded): every rank learns of any rank's failure
+  c->def.active = false;
+  // the walk sets' kept indexes and sort results were built by this expansion's schedule: the next user rebuilds
+  c->nnw_built.n = -1;
+  c->nnw.sorted_n = c->nnw_alt.sorted_n = c->nnw3.sorted_n = -1;
+  x.st.nodes_added = c->n_nodes - x.nodes_before;
+  x.st.elapsed_ms = x.ms_since(x.t0);
+  *rng = x.committed;
+  if (out) *out = x.st;
+  return rc;
+}
+
 static int expand_lag2(clrrt_ctx* c, clrrt_rng* rng, int64_t n_iters, double budget_ms, int32_t batch,
                        clrrt_stats* out) {
   int rc = lag_alloc(c);
   if (rc == CLRRT_OK && c->nn_delta_walk) rc = alloc_walk_delta(c);
   if (rc == CLRRT_OK) rc = apply_stream_prio(c);
-  if (rc == CLRRT_OK) rc = defer_begin(c, true);
   if (rc != CLRRT_OK) return rc;
-  clrrt_stats st{};
-  const auto t0 = std::chrono::steady_clock::now();
-  clrrt_rng work = *rng, committed = *rng;
-  std::deque<clrrt_sample> pending;
+  ExpandRun x(c, *rng, n_iters, budget_ms);
+  rc = expand_begin(x, true);
   const int cur = batch;  // samples per round, all ranks
-  const bool sharded = c->sh.fn != nullptr;
-  c->sh.max_ms = 0;
-  c->sh.nd_global = 0;
-  c->sh.rows_stop = 0;
-  shard_expansion_begin(c);
-  if (sharded && (rc = shard_goal_reset(c)) != CLRRT_OK) return rc;
-  const int64_t nodes_before = c->n_nodes;
+  const bool sharded = x.sharded;
   hipStream_t sides[2] = {c->side, c->side2};
   WalkBufs* W[3] = {&c->nnw, &c->nnw_alt, &c->nnw3};
-  int64_t built_n[3] = {-1, -1, -1};  // the tree size each walk set's index was built for
-  double built_f[3][7] = {};           // ... and its frame (fr.ox, fr.oy, fr.delta, x0, y0, x1, y1)
-  // list sets: this round's (c->*), round r+1's (A) and round r+2's (B)
+  BuiltFor built[3];  // what each walk set's index was built for
+  // list sets: this round's (ls[0]), round r+1's (slot A: ls[1]) and round r+2's (slot B: ls[2])
   LagSlot A, B;
-  A.d = c->d_samples2; A.h = c->h_samples2; A.cand = c->cand2; A.ckey = c->ckey2; A.ncand = c->ncand2;
-  A.ctie = c->ctie2; A.ev = c->ev_lag[0]; A.evw = c->ev_lagw[0];
-  B.d = c->d_samples3; B.h = c->h_samples3; B.cand = c->cand3; B.ckey = c->ckey3; B.ncand = c->ncand3;
-  B.ctie = c->ctie3; B.ev = c->ev_lag[1]; B.evw = c->ev_lagw[1];
-  A.wseed = c->wseed[0]; A.evm = c->ev_wm[0];
-  B.wseed = c->wseed[1]; B.evm = c->ev_wm[1];
-  float* cur_wseed = c->wseed[2];
-  hipEvent_t cur_evm = c->ev_wm[2];
+  A.set = c->ls[1];
+  B.set = c->ls[2];
   const bool early = c->nn_delta_early != 0;
-  hipEvent_t cur_ev = c->ev_lag[2];  // the event of the set this round's lists are in
-  hipEvent_t cur_evw = c->ev_lagw[2];
   // The appended-node search walks its range's own index (nn_delta_walk) from one tile of appended nodes on: a range
   // inside one tile has a single bound, so the walk would prefilter every record as k_nn_partial does, behind three
   // more launches (a range above the set's capacity takes the brute force too).
   const int64_t delta_walk_min = 32;
   const bool delta_walk = c->nn_delta_walk != 0;
-  // The three list sets rotate every round; whichever way the function is left (an error return of HIPC
-  // included), the buffers the context's other paths use get their roles back: (d_samples, cand, ...) and
-  // the *2 set are whichever two of the three sets, *3 the third, each freed once by free_all.
-  struct RoleGuard {
-    std::function<void()> f;
-    ~RoleGuard() { f(); }
-  } role_guard{[&]() {
-    c->d_samples2 = A.d; c->h_samples2 = A.h; c->cand2 = A.cand; c->ckey2 = A.ckey; c->ncand2 = A.ncand; c->ctie2 = A.ctie;
-    c->d_samples3 = B.d; c->h_samples3 = B.h; c->cand3 = B.cand; c->ckey3 = B.ckey; c->ncand3 = B.ncand; c->ctie3 = B.ctie;
-    c->ev_lag[0] = A.ev; c->ev_lag[1] = B.ev; c->ev_lag[2] = cur_ev;
-    c->ev_lagw[0] = A.evw; c->ev_lagw[1] = B.evw; c->ev_lagw[2] = cur_evw;
-    c->nnw_built.n = -1;
-    c->nnw.sorted_n = -1;
-    c->nnw_alt.sorted_n = -1;
-    c->nnw3.sorted_n = -1;
-  }};
-  bool have_cur = false;             // this round's lists come from slot A of the previous round
+  bool have_cur = false;  // this round's lists come from slot A of the previous round
   int cur_stream = 0;
-  double last_round_ms = 0;
-  auto frame_of = [](const NnSetup& su, double* f) {
-    f[0] = su.fr.ox; f[1] = su.fr.oy; f[2] = su.fr.delta; f[3] = su.x0; f[4] = su.y0; f[5] = su.x1; f[6] = su.y1;
-  };
   // the index of the tree as it is now into walk set k (incremental from the set built before, if any)
   auto build = [&](int k, const NnSetup& su) -> int {
-    double f[7];
-    frame_of(su, f);
-    if (built_n[k] == c->n_nodes && std::equal(f, f + 7, built_f[k])) return CLRRT_OK;
+    if (tree_index_matches(c, built[k], su)) return CLRRT_OK;
     int r2 = ensure_walk_set(c, *W[k]);
     if (r2 != CLRRT_OK) return r2;
     const WalkBufs* prev = nullptr;
@@ -3226,66 +3296,44 @@ static int expand_lag2(clrrt_ctx* c, clrrt_rng* rng, int64_t n_iters, double bud
     }
     KTimer kt(c, 0, c->stream);
     HIPC(c, launch_nn_walk_build(c->stream, c->nn, (int)c->n_nodes, su.fr, su.x0, su.y0, su.x1, su.y1, *W[k], prev));
-    built_n[k] = c->n_nodes;
-    std::copy(f, f + 7, built_f[k]);
+    tree_index_set(c, built[k], su);
     return CLRRT_OK;
   };
-  // slot sl: the walk search of its n samples (host copy sl.h) over the current tree (walk set k)
+  // slot sl: the walk search of its n samples (its set's host copy) over the current tree (walk set k)
   auto walk = [&](LagSlot& sl, int n, int k, const NnSetup& su, int si) -> int {
     hipStream_t s = sides[si];
+    ListSet& l = *sl.set;
     int r2 = ensure_walk_set(c, *W[k]);  // the configuration (budgets) for this tree size
     if (r2 != CLRRT_OK) return r2;
     c->nn_bf_keys += (int64_t)n * c->n_nodes;
     c->nn_samples += n;
     HIPC(c, hipStreamWaitEvent(s, c->ev_tree, 0));
-    HIPC(c, hipMemcpyAsync(sl.d, sl.h, sizeof(clrrt_sample) * n, hipMemcpyHostToDevice, s));
+    HIPC(c, hipMemcpyAsync(l.d_samples, l.h_samples, sizeof(clrrt_sample) * n, hipMemcpyHostToDevice, s));
     c->nn_super_bounds += (int64_t)n * walk_super_count(c->n_nodes);
     {
       KTimer kt(c, 0, s), kt3(c, 3, s);
-      W[k]->seed_out = early ? sl.wseed : nullptr;
-      W[k]->ev_main = early ? sl.evm : nullptr;
-      const hipError_t ew = launch_nn_walk_search(s, sl.d, n, c->nn, (int)c->n_nodes, c->dp, su.fr, su.x0, su.y0, su.x1,
-                                                  su.y1, *W[k], sl.cand, sl.ckey, sl.ncand, sl.ctie, c->work_ctr + 18,
+      W[k]->seed_out = early ? l.wseed : nullptr;
+      W[k]->ev_main = early ? l.evm : nullptr;
+      const hipError_t ew = launch_nn_walk_search(s, l.d_samples, n, c->nn, (int)c->n_nodes, c->dp, su.fr, su.x0, su.y0,
+                                                  su.x1, su.y1, *W[k], l.cand, l.ckey, l.ncand, l.ctie, c->work_ctr + 18,
                                                   c->nnw_stateless);
       W[k]->seed_out = nullptr;
       W[k]->ev_main = nullptr;
       HIPC(c, ew);
     }
-    HIPC(c, hipEventRecord(sl.evw, s));
+    HIPC(c, hipEventRecord(l.evw, s));
     sl.n = n;
     sl.tree_n = c->n_nodes;
     sl.stream = si;
     return CLRRT_OK;
   };
-  auto draw_to = [&](int64_t want) {
-    while ((int64_t)pending.size() < want) {
-      clrrt_sample smp;
-      clrrt_draw_samples(&c->params, &work, 1, &smp);
-      pending.push_back(smp);
-    }
-  };
-  for (int64_t k = 0; rc == CLRRT_OK; k++) {
-    const auto tr0 = std::chrono::steady_clock::now();
-    if (n_iters > 0 && st.iterations >= n_iters) break;
-    const double ms0 = std::chrono::duration<double, std::milli>(tr0 - t0).count();
-    // sharded: every rank decides on the largest elapsed time over the ranks (the same rounds everywhere)
-    if (n_iters == 0 && !((sharded ? c->sh.max_ms : ms0) < budget_ms)) break;
-    const int64_t left = n_iters > 0 ? n_iters - st.iterations : INT64_MAX;
-    // gb samples this round over all ranks; this rank's slice [f0, f0 + nb)
-    const int64_t gb = std::min<int64_t>(cur, left);
-    int64_t f0 = 0;
-    int nb = (int)gb;
-    if (sharded) shard_slice(c, gb, &f0, &nb);
-    c->sh.last_nb = nb;
-    // (a commit also takes the deferred samples that resolve; sharded, the stop decision must be the same
-    // on every rank: node counts only, the deferred samples bounded by the ring's rounds)
-    const int64_t nc = gb + (sharded ? c->sh.nd_global : (int64_t)c->def.nd);
-    if (c->n_nodes + 2 * nc > c->cap.max_nodes ||
-        (sharded ? c->sh.rows_stop > 0 : c->n_rows + 2 * nc * (c->dp.n_steps_max + 1) > c->cap.max_rows)) {
-      if (n_iters > 0) { rc = fail(c, CLRRT_ECAPACITY, "tree capacity exhausted"); break; }
-      st.capacity_stop = 1;
-      break;
-    }
+  // round k: gb samples over all ranks, this rank's slice [f0, f0 + nb)
+  auto round = [&](int64_t k, int64_t gb, int64_t f0, int nb) -> int {
+    int r = CLRRT_OK;
+    auto& pending = x.pending;
+    ListSet& cs = *c->ls[0];
+    const int64_t left = n_iters > 0 ? n_iters - x.st.iterations : INT64_MAX;
+    const double ms0 = x.ms0;
     const int wk = (int)(k % 3);
     const NnSetup su = nn_setup(c);
     const bool serve = c->n_nodes >= c->nnw_min_nodes && su.region_ok;
@@ -3294,8 +3342,8 @@ static int expand_lag2(clrrt_ctx* c, clrrt_rng* rng, int64_t n_iters, double bud
     int64_t gA = 0, gB = 0, fA = 0, fB = 0;
     int nA = 0, nB = 0;
     if (serve) {
-      const bool more = n_iters > 0 || ms0 + 2.0 * last_round_ms < budget_ms;
-      if (A.n == 0 && (n_iters > 0 || ms0 + last_round_ms < budget_ms)) gA = std::max<int64_t>(0, std::min<int64_t>(cur, left - gb));
+      const bool more = n_iters > 0 || ms0 + 2.0 * x.last_round_ms < budget_ms;
+      if (A.n == 0 && (n_iters > 0 || ms0 + x.last_round_ms < budget_ms)) gA = std::max<int64_t>(0, std::min<int64_t>(cur, left - gb));
       const int64_t gA_eff = A.n > 0 ? A.g : gA;
       if (more && gA_eff > 0) gB = std::max<int64_t>(0, std::min<int64_t>(cur, left - gb - gA_eff));
       nA = (int)gA;
@@ -3306,44 +3354,44 @@ static int expand_lag2(clrrt_ctx* c, clrrt_rng* rng, int64_t n_iters, double bud
       }
     }
     const int64_t gA_all = A.n > 0 ? A.g : gA;
-    draw_to(gb + gA_all + gB);
+    draw_to(x, gb + gA_all + gB);
     // this round's lists
     if (have_cur) {
       KTimer kt(c, 4);  // the lists' wait (time the main stream stalls on the side streams)
-      HIPC(c, hipStreamWaitEvent(c->stream, cur_ev, 0));
+      HIPC(c, hipStreamWaitEvent(c->stream, cs.ev, 0));
     } else {
-      for (int j = 0; j < nb; j++) c->h_samples[j] = pending[f0 + j];
-      HIPC(c, hipMemcpyAsync(c->d_samples, c->h_samples, sizeof(clrrt_sample) * nb, hipMemcpyHostToDevice, c->stream));
+      for (int j = 0; j < nb; j++) cs.h_samples[j] = pending[f0 + j];
+      HIPC(c, hipMemcpyAsync(cs.d_samples, cs.h_samples, sizeof(clrrt_sample) * nb, hipMemcpyHostToDevice, c->stream));
       if (serve) {
         // the side streams' work is done (a first pipelined round searches nothing ahead yet)
         HIPC(c, hipStreamSynchronize(c->side));
         HIPC(c, hipStreamSynchronize(c->side2));
         HIPC(c, hipStreamSynchronize(c->mst));
-        if ((rc = build(wk, su)) != CLRRT_OK) break;
+        if ((r = build(wk, su)) != CLRRT_OK) return r;
         c->nn_bf_keys += (int64_t)nb * c->n_nodes;
         c->nn_samples += nb;
         c->nn_super_bounds += (int64_t)nb * walk_super_count(c->n_nodes);
         KTimer kt(c, 0), kt3(c, 3);
-        HIPC(c, launch_nn_walk_search(c->stream, c->d_samples, nb, c->nn, (int)c->n_nodes, c->dp, su.fr, su.x0, su.y0,
-                                      su.x1, su.y1, *W[wk], c->cand, c->ckey, c->ncand, c->ctie, c->work_ctr + 18,
+        HIPC(c, launch_nn_walk_search(c->stream, cs.d_samples, nb, c->nn, (int)c->n_nodes, c->dp, su.fr, su.x0, su.y0,
+                                      su.x1, su.y1, *W[wk], cs.cand, cs.ckey, cs.ncand, cs.ctie, c->work_ctr + 18,
                                       c->nnw_stateless));
-      } else if ((rc = run_nn(c, nb, nullptr)) != CLRRT_OK) {
-        break;
+      } else if ((r = run_nn(c, nb, nullptr)) != CLRRT_OK) {
+        return r;
       }
     }
-    if (serve && (nA > 0 || nB > 0) && (rc = build(wk, su)) != CLRRT_OK) break;
+    if (serve && (nA > 0 || nB > 0) && (r = build(wk, su)) != CLRRT_OK) return r;
     // searches ahead, beside this round's rollouts: slot A's (bootstrap) then slot B's; B on the other
     // side stream than A, except when both search this round's index (the walk set's sample scratch
     // is shared: one stream)
     auto ahead = [&]() -> int {
       if (nA > 0) {
-        for (int j = 0; j < nA; j++) A.h[j] = pending[gb + fA + j];
+        for (int j = 0; j < nA; j++) A.set->h_samples[j] = pending[gb + fA + j];
         const int r2 = walk(A, nA, wk, su, cur_stream);
         if (r2 != CLRRT_OK) return r2;
         A.g = gA;
       }
       if (nB > 0) {
-        for (int j = 0; j < nB; j++) B.h[j] = pending[gb + gA_all + fB + j];
+        for (int j = 0; j < nB; j++) B.set->h_samples[j] = pending[gb + gA_all + fB + j];
         const int r2 = walk(B, nB, wk, su, nA > 0 ? A.stream : 1 - A.stream);
         if (r2 != CLRRT_OK) return r2;
         B.g = gB;
@@ -3351,21 +3399,23 @@ static int expand_lag2(clrrt_ctx* c, clrrt_rng* rng, int64_t n_iters, double bud
       return CLRRT_OK;
     };
     int L = nb, nn = 0, n_app = 0;
-    if ((rc = eval_samples(c, nb, false, &L, true, (nA > 0 || nB > 0) ? std::function<int()>(ahead) : nullptr,
-                           nullptr)) != CLRRT_OK)
-      break;
-    if ((rc = compact_and_copy(c, L, &nn, true)) != CLRRT_OK) break;
-    const double ms_commit = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    if ((rc = commit_round(c, nn, ms_commit, &n_app)) != CLRRT_OK) break;
+    if ((r = eval_samples(c, nb, false, &L, true, (nA > 0 || nB > 0) ? std::function<int()>(ahead) : nullptr,
+                          nullptr)) != CLRRT_OK)
+      return r;
+    if ((r = compact_and_copy(c, L, &nn, true)) != CLRRT_OK) return r;
+    if ((r = commit_round(c, nn, x.ms_since(x.t0), &n_app)) != CLRRT_OK) return r;
+    if (c->fail_in_round > 0 && --c->fail_in_round == 0)
+      return fail(c, CLRRT_ECAPACITY, "injected failure (option fail_in_round)");
     // slot A: merge the nodes appended since its walk's tree.  On the merge stream, behind the commit and -- early --
     // slot A's main walk grid (caps from its k_walk_seed, beside the walk's overflow split) or the whole walk (caps from
     // its list); the merge behind the whole walk.  The search walks the range's own index (launch_nn_delta_walk) where
     // the walk is served (region, tree size) and the range is neither tiny nor beyond the set; else the brute force.
     if (A.n > 0) {
+      ListSet& a = *A.set;
       HIPC(c, hipEventRecord(c->ev_commit, c->stream));
       hipStream_t s = c->mst;
       HIPC(c, hipStreamWaitEvent(s, c->ev_commit, 0));
-      HIPC(c, hipStreamWaitEvent(s, early ? A.evm : A.evw, 0));
+      HIPC(c, hipStreamWaitEvent(s, early ? a.evm : a.evw, 0));
       const int64_t first = A.tree_n, cnt = c->n_nodes - A.tree_n;
       const NnSetup su2 = nn_setup(c);
       const bool dwalk = delta_walk && su2.region_ok && c->n_nodes >= c->nnw_min_nodes && cnt >= delta_walk_min &&
@@ -3375,87 +3425,59 @@ static int expand_lag2(clrrt_ctx* c, clrrt_rng* rng, int64_t n_iters, double bud
       if (cnt > 0) c->nn_bf_keys += (int64_t)A.n * cnt;
       if (cnt > 0 && dwalk) {
         KTimer kt(c, 0, s);
-        float* seed = early ? A.wseed : c->nn_seed;
+        float* seed = early ? a.wseed : c->nn_seed;
         const bool verify = c->nn_delta_verify && c->vseed;
-        HIPC(c, launch_nn_delta_walk(s, A.d, A.n, c->nn, (int)first, (int)cnt, c->dp, su2.fr, su2.x0, su2.y0, su2.x1,
-                                     su2.y1, c->nnw_d, c->pk, c->pi, A.ckey, A.ncand, seed, early,
+        HIPC(c, launch_nn_delta_walk(s, a.d_samples, A.n, c->nn, (int)first, (int)cnt, c->dp, su2.fr, su2.x0, su2.y0,
+                                     su2.x1, su2.y1, c->nnw_d, c->pk, c->pi, a.ckey, a.ncand, seed, early,
                                      verify ? c->work_ctr + 40 : nullptr));
         nch = 1;
         id0 = 0;
         if (verify) {  // the brute force over the same range and caps, and the two list sets compared
           int vch = 0;
           HIPC(c, hipMemcpyAsync(c->vseed, seed, sizeof(float) * A.n, hipMemcpyDeviceToDevice, s));
-          HIPC(c, launch_nn_delta_partial(s, A.d, A.n, c->nn, (int)first, (int)cnt, c->dp, su2.fr, c->vpk, c->vpi,
-                                          max_chunks, nullptr, nullptr, c->vseed, true, nullptr, &vch, c->work_ctr + 52));
+          HIPC(c, launch_nn_delta_partial(s, a.d_samples, A.n, c->nn, (int)first, (int)cnt, c->dp, su2.fr, c->vpk,
+                                          c->vpi, max_chunks, nullptr, nullptr, c->vseed, true, nullptr, &vch,
+                                          c->work_ctr + 52));
           HIPC(c, launch_nn_delta_compare(s, A.n, vch, (int)first, c->vpk, c->vpi, c->pk, c->pi, c->work_ctr + 38));
         }
       } else if (cnt > 0 && early) {
         KTimer kt(c, 0, s);
-        HIPC(c, launch_nn_delta_partial(s, A.d, A.n, c->nn, (int)first, (int)cnt, c->dp, su2.fr, c->pk, c->pi,
-                                        max_chunks, nullptr, nullptr, A.wseed, true,
+        HIPC(c, launch_nn_delta_partial(s, a.d_samples, A.n, c->nn, (int)first, (int)cnt, c->dp, su2.fr, c->pk, c->pi,
+                                        max_chunks, nullptr, nullptr, a.wseed, true,
                                         c->nn_lane_order ? c->nn_order : nullptr, &nch));
       } else if (cnt > 0) {
         KTimer kt(c, 0, s);
-        HIPC(c, launch_nn_delta(s, A.d, A.n, c->nn, (int)first, (int)cnt, c->dp, su2.fr, c->pk, c->pi, max_chunks,
-                                A.cand, A.ckey, A.ncand, A.ctie, c->nn_seed));
+        HIPC(c, launch_nn_delta(s, a.d_samples, A.n, c->nn, (int)first, (int)cnt, c->dp, su2.fr, c->pk, c->pi,
+                                max_chunks, a.cand, a.ckey, a.ncand, a.ctie, c->nn_seed));
       }
-      if (early) HIPC(c, hipStreamWaitEvent(s, A.evw, 0));
+      if (early) HIPC(c, hipStreamWaitEvent(s, a.evw, 0));
       if (nch > 0) {
         KTimer kt(c, 0, s);
-        HIPC(c, launch_nn_delta_merge(s, A.n, nch, c->dp, c->pk, c->pi, id0, A.cand, A.ckey, A.ncand, A.ctie));
+        HIPC(c, launch_nn_delta_merge(s, A.n, nch, c->dp, c->pk, c->pi, id0, a.cand, a.ckey, a.ncand, a.ctie));
       }
-      HIPC(c, hipEventRecord(A.ev, s));
+      HIPC(c, hipEventRecord(a.ev, s));
     }
     // the next round's index (the walk of round r+3's samples searches it)
     {
       const NnSetup sn = nn_setup(c);
-      if (B.n > 0 && c->n_nodes >= c->nnw_min_nodes && sn.region_ok && (rc = build((int)((k + 1) % 3), sn)) != CLRRT_OK)
-        break;
+      if (B.n > 0 && c->n_nodes >= c->nnw_min_nodes && sn.region_ok && (r = build((int)((k + 1) % 3), sn)) != CLRRT_OK)
+        return r;
     }
-    for (int64_t j = 0; j < gb; j++) {
-      pending.pop_front();
-      for (int q = 0; q < 3; q++) clrrt_rng_next(&committed);
-    }
-    st.iterations += gb;
-    st.goal_nodes_added += c->last_goal_nodes;
-    st.speculated += gb;
-    st.rounds++;
-    // rotate: A becomes this round's set, B slot A, this round's set slot B
-    {
-      LagSlot old;
-      old.d = c->d_samples; old.h = c->h_samples; old.cand = c->cand; old.ckey = c->ckey; old.ncand = c->ncand;
-      old.ctie = c->ctie; old.ev = cur_ev; old.evw = cur_evw; old.stream = cur_stream;
-      old.wseed = cur_wseed; old.evm = cur_evm;
-      have_cur = A.n > 0;
-      c->d_samples = A.d; c->h_samples = A.h; c->cand = A.cand; c->ckey = A.ckey; c->ncand = A.ncand; c->ctie = A.ctie;
-      cur_ev = A.ev;
-      cur_evw = A.evw;
-      cur_stream = A.stream;
-      cur_wseed = A.wseed; cur_evm = A.evm;
-      A = B;
-      B = old;
-      B.n = 0;
-      B.stream = 1 - A.stream;
-    }
-    last_round_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tr0).count();
-  }
-  // the deferred samples still pending and the last round's accepted rows (part of the query's output
-  // tree, so inside its time)
-  if (rc == CLRRT_OK) rc = defer_drain(c, &st.goal_nodes_added);
-  st.deferred = c->def.deferred_total;
-  if (rc == CLRRT_OK) rc = flush_replays(c);
-  if (rc == CLRRT_OK && sharded) rc = shard_goal_count(c, &st.goal_nodes_added);
-  rc = shard_expansion_end(c, rc);  // the closing exchange (sharded): every rank learns of any rank's failure
-  c->def.active = false;
-  for (hipStream_t s : {c->side, c->side2, c->mst, c->stream}) {  // every stream drained, the first error kept
-    const hipError_t e = hipStreamSynchronize(s);
-    if (e != hipSuccess && rc == CLRRT_OK) rc = fail(c, CLRRT_EHIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(e));
-  }
-  st.nodes_added = c->n_nodes - nodes_before;
-  st.elapsed_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  *rng = committed;
-  if (out) *out = st;
-  return rc;
+    round_done(x, gb, gb);
+    // rotate: slot A's set becomes this round's, slot B becomes slot A, this round's set serves the new slot B
+    have_cur = A.n > 0;
+    cur_stream = A.stream;
+    std::rotate(c->ls, c->ls + 1, c->ls + 3);
+    A = B;
+    B = LagSlot{};
+    B.set = c->ls[2];
+    B.stream = 1 - A.stream;
+    return CLRRT_OK;
+  };
+  int64_t gb = 0, f0 = 0;
+  int nb = 0;
+  for (int64_t k = 0; rc == CLRRT_OK && round_plan(x, cur, &rc, &gb, &f0, &nb); k++) rc = round(k, gb, f0, nb);
+  return expand_end(x, rc, rng, out);
 }
 
 int clrrt_expand(clrrt_ctx* c, clrrt_rng* rng, int64_t n_iters, double budget_ms, int32_t mode, int32_t batch,
@@ -3475,57 +3497,21 @@ int clrrt_expand(clrrt_ctx* c, clrrt_rng* rng, int64_t n_iters, double budget_ms
   const int lag = c->nn_lag ? c->nn_lag
                   : (n_iters == 0 ? budget_ms >= 1000.0 : n_iters >= 64 * (int64_t)batch) ? 2 : 1;
   if (mode == CLRRT_MODE_BATCH && c->nn_pipeline && lag == 2) return expand_lag2(c, rng, n_iters, budget_ms, batch, out);
-  clrrt_stats st{};
-  auto t0 = std::chrono::steady_clock::now();
-  clrrt_rng work = *rng;       // draws ahead (speculative samples)
-  clrrt_rng committed = *rng;  // state after exactly `iterations` iterations
-  std::deque<clrrt_sample> pending;
+  ExpandRun x(c, *rng, n_iters, budget_ms);
   const bool exact = mode == CLRRT_MODE_EXACT;
   int cur = exact ? std::min(batch, std::max(16, c->exact_min_width)) : batch;
-  int64_t nodes_before = c->n_nodes;
-  int rc = defer_begin(c, !exact);
-  c->sh.max_ms = 0;
-  c->sh.nd_global = 0;
-  c->sh.rows_stop = 0;
-  shard_expansion_begin(c);
-  if (rc == CLRRT_OK && sharded) rc = shard_goal_reset(c);
+  int rc = expand_begin(x, !exact);
   bool have_next = false;  // this round's samples and lists were prepared by the previous round
-  double last_round_ms = 0;
-  auto draw_to = [&](int64_t want) {
-    while ((int64_t)pending.size() < want) {
-      clrrt_sample smp;
-      clrrt_draw_samples(&c->params, &work, 1, &smp);
-      pending.push_back(smp);
-    }
-  };
-  for (; rc == CLRRT_OK;) {
-    const auto tr0 = std::chrono::steady_clock::now();
-    if (n_iters > 0 && st.iterations >= n_iters) break;
-    if (n_iters == 0) {
-      double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-      // sharded: every rank decides on the largest elapsed time over the ranks (the same rounds everywhere)
-      if (!((sharded ? c->sh.max_ms : ms) < budget_ms)) break;
-    }
-    // gb samples this round over all ranks; this rank's slice [f0, f0 + nb)
-    int64_t gb = cur;
-    if (n_iters > 0) gb = std::min<int64_t>(gb, n_iters - st.iterations);
-    int64_t f0 = 0;
-    int nb = (int)gb;
-    if (sharded) shard_slice(c, gb, &f0, &nb);
-    c->sh.last_nb = nb;
-    // a round appends at most 2 nodes and 2 full-horizon trajectories per sample (+ the deferred samples;
-    // sharded, the same decision on every rank: node counts only, deferred samples bounded by the ring)
-    const int64_t nc = gb + (sharded ? c->sh.nd_global : (int64_t)c->def.nd);
-    if (c->n_nodes + 2 * nc > c->cap.max_nodes ||
-        (sharded ? c->sh.rows_stop > 0 : c->n_rows + 2 * nc * (c->dp.n_steps_max + 1) > c->cap.max_rows)) {
-      if (n_iters > 0) { rc = fail(c, CLRRT_ECAPACITY, "tree capacity exhausted"); break; }
-      st.capacity_stop = 1;
-      break;
-    }
-    draw_to(gb);
+  // one round: gb samples over all ranks, this rank's slice [f0, f0 + nb)
+  auto round = [&](int64_t gb, int64_t f0, int nb) -> int {
+    int r = CLRRT_OK;
+    auto& pending = x.pending;
+    const auto& st = x.st;
+    draw_to(x, gb);
     if (!have_next) {
-      for (int j = 0; j < nb; j++) c->h_samples[j] = pending[f0 + j];
-      HIPC(c, hipMemcpyAsync(c->d_samples, c->h_samples, sizeof(clrrt_sample) * nb, hipMemcpyHostToDevice, c->stream));
+      ListSet& cs = *c->ls[0];
+      for (int j = 0; j < nb; j++) cs.h_samples[j] = pending[f0 + j];
+      HIPC(c, hipMemcpyAsync(cs.d_samples, cs.h_samples, sizeof(clrrt_sample) * nb, hipMemcpyHostToDevice, c->stream));
     }
     // Pipelined BATCH rounds: the next round's samples are known now (BATCH rounds commit every
     // sample), so their walk search over this round's tree runs on the side stream while this round's
@@ -3538,10 +3524,7 @@ int clrrt_expand(clrrt_ctx* c, clrrt_rng* rng, int64_t n_iters, double budget_ms
     if (!exact && c->nn_pipeline) {
       gb2 = cur;
       if (n_iters > 0) gb2 = std::max<int64_t>(0, std::min<int64_t>(gb2, n_iters - st.iterations - gb));
-      if (n_iters == 0) {
-        double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        if (!(ms + last_round_ms < budget_ms)) gb2 = 0;  // this is probably the last round
-      }
+      if (n_iters == 0 && !(x.ms_since(x.t0) + x.last_round_ms < budget_ms)) gb2 = 0;  // this is probably the last round
       nb2 = (int)gb2;
       if (sharded) shard_slice(c, gb2, &f2, &nb2);
       if (nb2 > 0) {
@@ -3550,61 +3533,43 @@ int clrrt_expand(clrrt_ctx* c, clrrt_rng* rng, int64_t n_iters, double budget_ms
       }
     }
     auto prefetch = [&]() -> int {
-      draw_to(gb + gb2);
-      for (int j = 0; j < nb2; j++) c->h_samples2[j] = pending[gb + f2 + j];
+      draw_to(x, gb + gb2);
+      for (int j = 0; j < nb2; j++) c->ls[1]->h_samples[j] = pending[gb + f2 + j];
       return launch_side_walk(c, nb2, su);
     };
     int L = nb, nn = 0, n_app = 0;
     auto build = [&]() -> int { return pre_roll_build(c, su); };
-    if ((rc = eval_samples(c, nb, exact, &L, have_next, nb2 > 0 ? std::function<int()>(prefetch) : nullptr,
-                           nb2 > 0 ? std::function<int()>(build) : nullptr)) != CLRRT_OK)
-      break;
+    if ((r = eval_samples(c, nb, exact, &L, have_next, nb2 > 0 ? std::function<int()>(prefetch) : nullptr,
+                          nb2 > 0 ? std::function<int()>(build) : nullptr)) != CLRRT_OK)
+      return r;
     if (!exact) {
       // BATCH rounds commit every sample, so the next round's samples are known now: draw them
       // while the GPU evaluates this round (the draw is ~0.05 us per sample on the host)
       int64_t want = gb + (int64_t)cur;
       if (n_iters > 0) want = std::min<int64_t>(want, n_iters - st.iterations);
-      draw_to(want);
+      draw_to(x, want);
     }
-    if ((rc = compact_and_copy(c, L, &nn, true)) != CLRRT_OK) break;
+    if ((r = compact_and_copy(c, L, &nn, true)) != CLRRT_OK) return r;
     const int64_t first_new = c->n_nodes;
-    const double ms_commit = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    if ((rc = commit_round(c, nn, ms_commit, &n_app)) != CLRRT_OK) break;
+    if ((r = commit_round(c, nn, x.ms_since(x.t0), &n_app)) != CLRRT_OK) return r;
+    if (c->fail_in_round > 0 && --c->fail_in_round == 0)
+      return fail(c, CLRRT_ECAPACITY, "injected failure (option fail_in_round)");
     have_next = false;
     if (nb2 > 0) {
-      if ((rc = side_delta_launch(c, nb2, first_new, n_app)) != CLRRT_OK) break;
-      if (c->nnw_double && (rc = next_round_build(c)) != CLRRT_OK) break;
-      if ((rc = side_lists_join(c)) != CLRRT_OK) break;
+      if ((r = side_delta_launch(c, nb2, first_new, n_app)) != CLRRT_OK) return r;
+      if (c->nnw_double && (r = next_round_build(c)) != CLRRT_OK) return r;
+      if ((r = side_lists_join(c)) != CLRRT_OK) return r;
       have_next = true;
     }
     // iterations consumed: the committed prefix (EXACT) or the whole round (BATCH, every rank's samples)
-    const int64_t used = exact ? L : gb;
-    for (int64_t j = 0; j < used; j++) {
-      pending.pop_front();
-      for (int k = 0; k < 3; k++) clrrt_rng_next(&committed);
-    }
-    st.iterations += used;
-    st.goal_nodes_added += c->last_goal_nodes;
-    st.speculated += exact ? nb : gb;
-    st.rounds++;
+    round_done(x, exact ? L : gb, exact ? nb : gb);
     if (exact) cur = std::max(c->exact_min_width, std::min(batch, L == nb ? 2 * nb : 2 * L));
-    last_round_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tr0).count();
-  }
-  // the deferred samples still pending and the last round's accepted rows (part of the query's output
-  // tree, so inside its time)
-  if (rc == CLRRT_OK) rc = defer_drain(c, &st.goal_nodes_added);
-  st.deferred = c->def.deferred_total;
-  if (rc == CLRRT_OK) rc = flush_replays(c);
-  if (rc == CLRRT_OK && sharded) rc = shard_goal_count(c, &st.goal_nodes_added);
-  rc = shard_expansion_end(c, rc);  // the closing exchange (sharded): every rank learns of any rank's failure
-  c->def.active = false;
-  HIPC(c, hipStreamSynchronize(c->side));
-  HIPC(c, hipStreamSynchronize(c->stream));
-  st.nodes_added = c->n_nodes - nodes_before;
-  st.elapsed_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  *rng = committed;
-  if (out) *out = st;
-  return rc;
+    return CLRRT_OK;
+  };
+  int64_t gb = 0, f0 = 0;
+  int nb = 0;
+  while (rc == CLRRT_OK && round_plan(x, cur, &rc, &gb, &f0, &nb)) rc = round(gb, f0, nb);
+  return expand_end(x, rc, rng, out);
 }
 
 int clrrt_set_shards(clrrt_ctx* c, int32_t rank, int32_t world, void* dev_local, int32_t cap_local,
@@ -3897,18 +3862,19 @@ int clrrt_nn_batch(clrrt_ctx* c, const clrrt_sample* samples, int32_t n, int32_t
                    float* out_keys) {
   if (!c || n < 0 || (n > 0 && (!samples || !out_ids))) return CLRRT_EINVAL;
   pf_reset(c);
+  ListSet& cur = *c->ls[0];
   if (mode != CLRRT_MODE_EXACT && mode != CLRRT_MODE_BATCH) return CLRRT_EINVAL;
   if (n > c->cap.max_batch) return fail(c, CLRRT_ECAPACITY, "batch larger than max_batch");
   HIPC(c, hipSetDevice(c->device));
   if (n == 0) return CLRRT_OK;
-  memcpy(c->h_samples, samples, sizeof(clrrt_sample) * n);
-  HIPC(c, hipMemcpyAsync(c->d_samples, c->h_samples, sizeof(clrrt_sample) * n, hipMemcpyHostToDevice, c->stream));
+  memcpy(cur.h_samples, samples, sizeof(clrrt_sample) * n);
+  HIPC(c, hipMemcpyAsync(cur.d_samples, cur.h_samples, sizeof(clrrt_sample) * n, hipMemcpyHostToDevice, c->stream));
   int rc = CLRRT_OK;
   if (mode == CLRRT_MODE_EXACT && (rc = ensure_sort_scratch(c, (int64_t)n * c->n_nodes)) != CLRRT_OK) return rc;
   if ((rc = run_nn(c, n, mode == CLRRT_MODE_EXACT ? c->sort_scratch : nullptr)) != CLRRT_OK) return rc;
-  HIPC(c, hipMemcpyAsync(out_ids, c->cand, sizeof(int) * CAND_K * n, hipMemcpyDeviceToHost, c->stream));
+  HIPC(c, hipMemcpyAsync(out_ids, cur.cand, sizeof(int) * CAND_K * n, hipMemcpyDeviceToHost, c->stream));
   if (out_keys)
-    HIPC(c, hipMemcpyAsync(out_keys, c->ckey, sizeof(float) * CAND_K * n, hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipMemcpyAsync(out_keys, cur.ckey, sizeof(float) * CAND_K * n, hipMemcpyDeviceToHost, c->stream));
   HIPC(c, hipStreamSynchronize(c->stream));
   return CLRRT_OK;
 }
@@ -3924,6 +3890,7 @@ int clrrt_round_sizes(clrrt_ctx* c, int64_t* out, int64_t cap, int64_t* n) {
 int clrrt_walk_audit(clrrt_ctx* c, const clrrt_sample* samples, int32_t n, int32_t* out) {
   if (!c || n < 0 || (n > 0 && (!samples || !out))) return CLRRT_EINVAL;
   pf_reset(c);
+  ListSet& cur = *c->ls[0];
   if (n > c->cap.max_batch) return fail(c, CLRRT_ECAPACITY, "batch larger than max_batch");
   HIPC(c, hipSetDevice(c->device));
   if (n == 0) return CLRRT_OK;
@@ -3931,13 +3898,13 @@ int clrrt_walk_audit(clrrt_ctx* c, const clrrt_sample* samples, int32_t n, int32
   if (!walk_serves(c, su)) return fail(c, CLRRT_ESTATE, "the walk does not serve this tree (too small or no region)");
   int rc = ensure_walk(c);
   if (rc != CLRRT_OK) return rc;
-  memcpy(c->h_samples, samples, sizeof(clrrt_sample) * n);
-  HIPC(c, hipMemcpyAsync(c->d_samples, c->h_samples, sizeof(clrrt_sample) * n, hipMemcpyHostToDevice, c->stream));
+  memcpy(cur.h_samples, samples, sizeof(clrrt_sample) * n);
+  HIPC(c, hipMemcpyAsync(cur.d_samples, cur.h_samples, sizeof(clrrt_sample) * n, hipMemcpyHostToDevice, c->stream));
   c->nnw_built.n = -1;
   HIPC(c, launch_nn_walk_build(c->stream, c->nn, (int)c->n_nodes, su.fr, su.x0, su.y0, su.x1, su.y1, c->nnw));
   int* d_out = nullptr;
   HIPC(c, hipMalloc(&d_out, sizeof(int32_t) * 20 * (size_t)n));
-  hipError_t e = launch_walk_audit(c->stream, c->d_samples, n, c->nn, (int)c->n_nodes, c->dp, su.fr, c->nnw, d_out);
+  hipError_t e = launch_walk_audit(c->stream, cur.d_samples, n, c->nn, (int)c->n_nodes, c->dp, su.fr, c->nnw, d_out);
   if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, sizeof(int32_t) * 20 * (size_t)n, hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
   hipFree(d_out);

@@ -595,7 +595,11 @@ int clrrt_enable_timing(clrrt_ctx* ctx, int32_t on);
  * "roll_priority" (1: a round of more rollout jobs than the grid has lanes is served by predicted length class,
  * default; 0: plain order), "roll_order_verify" (diagnostics), "roll_coop", "roll_spread", "roll_lanes",
  * "rows_deferred", "exact_min_width",
- * "cu_split", "walk_cu_reserve", "stream_prio", "side_priority" (see clrrt_capi.hip). */
+ * "cu_split", "walk_cu_reserve", "stream_prio", "side_priority" (see clrrt_capi.hip).
+ * Fault injection (tests; k > 0 arms it, the k-th event from now fails with CLRRT_ECAPACITY): "fail_at_round" (a
+ * round's commit, before its exchange), "fail_after_exchange" (after a round's exchange returned), "fail_in_round"
+ * (in clrrt_expand's round, right after its commit: where a HIP error of the work queued there would return).
+ * Option keys are strings: a new key changes no struct or signature and leaves CLRRT_ABI_VERSION as it is. */
 int clrrt_set_option(clrrt_ctx* ctx, const char* key, int64_t value);
 /* Nearest-node search diagnostics since the last clrrt_reset_counters.  out[0..6] unused (0).  Brute
  * force: out[7] (sample, node) pairs passing the float prefilter, out[8] exact Dubins keys evaluated.  Walk search: out[10] super-tiles visited, out[11]

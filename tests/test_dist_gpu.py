@@ -135,7 +135,8 @@ SHARD_CASES = [  # (ranks, samples per round over all ranks, defer_steps, nn_lag
 ]
 
 
-def _shard_worker(rank, port, out_dir, world, G, T, lag, rounds, fail_rank=-1, fail_round=0, fail_opt="fail_at_round"):
+def _shard_worker(rank, port, out_dir, world, G, T, lag, rounds, fail_rank=-1, fail_round=0, fail_opt="fail_at_round",
+                  opts=None):
     sys.path.insert(0, os.path.join(ROOT, "cl-rrt_amd"))
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
@@ -148,6 +149,8 @@ def _shard_worker(rank, port, out_dir, world, G, T, lag, rounds, fail_rank=-1, f
     pl = _planner(world)
     pl.set_option("defer_steps", T)
     pl.set_option("nn_lag", lag)
+    for k, v in (opts or {}).items():
+        pl.set_option(k, v)
     pl.set_stream(torch.cuda.current_stream().cuda_stream)
     ex = cdist.ShardExchange(pl, cdist.exchange_capacity(-(-G // world), T), "cuda", slice_size=-(-G // world))
     if rank == fail_rank:
@@ -244,6 +247,59 @@ def test_sharded_failure_after_last_exchange_is_collective(tmp_path, T, lag):
           f"{int(r0['ex_rounds'])} / {int(r1['ex_rounds'])}")
     assert "injected failure" in str(r1["err"])
     assert "rank(s) failed" in str(r0["err"])
+
+
+@pytest.mark.timeout(300)
+@pytest.mark.parametrize("fail_round", [2, 4])
+@pytest.mark.parametrize("T,lag", [(0, 1), (0, 2), (64, 2)])
+def test_sharded_failure_in_round_is_collective(tmp_path, T, lag, fail_round):
+    """A rank that fails inside a round of the driver, after the round's commit and exchange (option fail_in_round:
+    the return a HIP error of the work queued there takes), still reaches the expansion's epilogue: it joins the
+    exchange the other rank makes next -- the next round's, the drain's or the closing one -- with the error flag, so
+    both ranks leave with an error and neither waits in a collective.  nn_walk_min 256 puts the trees of these
+    rounds on the walk search, so the lag-2 searches ahead are in flight on the side streams at the failure."""
+    import torch.multiprocessing as mp
+    rounds = 4
+    mp.spawn(_shard_worker, args=(_free_port(), str(tmp_path), 2, 2 * B, T, lag, rounds, 1, fail_round,
+                                  "fail_in_round", {"nn_walk_min": 256}), nprocs=2, join=True)
+    r0, r1 = (np.load(tmp_path / f"shard{r}.npz") for r in range(2))
+    print(f"T={T} lag {lag}, fail in round {fail_round}: rank 0 '{r0['err']}', rank 1 '{r1['err']}', exchanges "
+          f"{int(r0['ex_rounds'])} / {int(r1['ex_rounds'])}")
+    assert "injected failure" in str(r1["err"])
+    assert "rank(s) failed" in str(r0["err"])
+
+
+@pytest.mark.timeout(300)
+@pytest.mark.parametrize("fail_round", [1, 2, 3])
+def test_failed_lag2_expansion_leaves_context_reusable(fail_round):
+    """A lag-2 expansion that fails in a round (one per phase of the three list sets' rotation, searches ahead in
+    flight) leaves the context's list sets in place: after rows_flush and tree_init a lag-2 and a lag-1 expansion
+    grow the trees a context that never failed grows, and closing the planner frees every set once."""
+    import clrrt
+    trees = []
+    for inject in (True, False):
+        pl = _planner(1)
+        pl.set_option("defer_steps", 32)
+        pl.set_option("nn_walk_min", 256)
+        pl.set_option("nn_lag", 2)
+        if inject:
+            pl.set_option("fail_in_round", fail_round)
+            with pytest.raises(clrrt.ClrrtError, match="injected failure"):
+                pl.expand(clrrt.Rng(5), n_iters=6 * B, mode=clrrt.CLRRT_MODE_BATCH, batch=B)
+            pl.rows_flush()
+            pl.tree_init()
+        got = []
+        for lag in (2, 1):
+            pl.set_option("nn_lag", lag)
+            st = pl.expand(clrrt.Rng(SEED), n_iters=4 * B, mode=clrrt.CLRRT_MODE_BATCH, batch=B)
+            assert st["rounds"] == 4 and st["deferred"] > 0
+            n, nr = pl.size()
+            got.append((bytes(pl.nodes_raw()), pl.rows(0, nr).tobytes()))
+            pl.tree_init()
+        trees.append(got)
+        pl.close()
+    assert trees[0][0] == trees[1][0]
+    assert trees[0][1] == trees[1][1]
 
 
 @pytest.mark.timeout(300)

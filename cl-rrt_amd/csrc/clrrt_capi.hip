@@ -56,7 +56,7 @@ struct ListSet {
   hipEvent_t ev = nullptr;   // recorded after the set's merge
   hipEvent_t evw = nullptr;  // recorded after its walk (the merge waits for it on the merge stream)
   hipEvent_t evm = nullptr;  // recorded after the walk's main grid (and wseed)
-  float* wseed = nullptr;    // [max_batch] nn_delta_early: the appended-node search's caps, taken after the main grid
+  float* wseed = nullptr;    // [max_batch] the appended-node search's caps, taken after the main grid
 };
 
 // Search region (the sampling region and the tree's box) and the float frame of the searches.
@@ -172,12 +172,10 @@ struct clrrt_ctx {
   // option "nn_walk_hscale": the 3D index codes' heading axis, percent of rho per radian (round 6: 25 / 50 / 100 / 200
   // -> cfg3 1.289 / 1.293 / 1.274 / 1.232 M nodes/s, profiles/r06k_*)
   int nnw_hscale = 50;
-  int nnw_lpt = 0;          // option "nn_walk_lpt": optimize samples first in each XCD's eighth (k_walk_lpt)
   int nnw_root_seed = 1;    // option "nn_root_seed": optimize samples start from the root roster (WalkBufs::roster)
   int nnw_root_k = 64;      // option "nn_root_k": roster entries
   int nnw_root_scan = 16384;  // option "nn_root_scan": ids scanned for them
   int nnw_index = 5;       // option "nn_walk_index": the index's place order (WalkBufs::index_kind); 5 since round 6
-  int nnw_lds_floor = 0;    // option "nn_walk_lds_floor": LDS bytes each walk wave reserves at least
   // option "nn_walk_waves": the walk's persistent grid (waves taking samples from per-XCD counters; 0 = one
   // wave per sample; -1, the default: 9 per CU).  A fixed grid leaves wave slots to the kernels that run
   // beside the lag-2 walk (the commit's k_select waited ~1.2 ms per round for slots behind ~1 ms walk waves)
@@ -263,12 +261,6 @@ struct clrrt_ctx {
   // then merges in the nodes it appended (launch_nn_delta) and ls[0] / ls[1] swap
   int nn_pipeline = 1;  // option "nn_pipeline"
   hipStream_t side = nullptr;
-  // option "cu_split" (k = 1..7): the rollouts run on their own stream restricted to k/8 of the CUs and
-  // the side stream (the next round's search) on the other CUs, so no search wave shares a SIMD with a
-  // rollout wave; 0: one unrestricted main stream for both (default)
-  int cu_split = 0;
-  hipStream_t roll_st = nullptr;
-  hipEvent_t ev_rs0 = nullptr, ev_rs1 = nullptr;
   hipEvent_t ev_tree = nullptr, ev_walk = nullptr, ev_commit = nullptr;
   // option "nn_lag" (1 or 2; 0 = by query length): how many rounds ahead the pipelined BATCH rounds search
   // (2: expand_lag2).  The default picks 2 for long queries (a budget of >= 1 s or >= 64 rounds), 1 for
@@ -310,19 +302,15 @@ struct clrrt_ctx {
   float* vpk = nullptr;    // nn_delta_verify: the brute force's chunk lists (partial_cap entries) ...
   int* vpi = nullptr;
   float* vseed = nullptr;  // ... and its copy of the caps (k_nn_partial lowers them)
-  // option "nn_delta_early" (default 1, round 6): the appended-node search of a slot starts after its walk's main grid
-  // (key caps from k_walk_seed, in the set's wseed) instead of after the overflow split and its merge, so it runs beside
-  // the split (a cfg3 trace: main grid done 1.7 ms before the rollout kernel, split until 0.6 ms after it, the search
-  // after that until 1.9 ms, profiles/r06w_cfg3_list_crit.txt); the merge still waits for the whole walk.
-  int nn_delta_early = 1;
-  // option "nn_lane_order" (default 1, round 6): the lag-2 appended-node search puts optimize samples on their own
-  // lanes (k_nn_order), so explore lanes do not idle while optimize lanes compute exact keys
-  int nn_lane_order = 1;
+  // Lag 2 (round 6): the appended-node search of a slot starts after its walk's main grid (key caps from k_walk_seed,
+  // in the set's wseed), not after the overflow split and its merge, so it runs beside the split (a cfg3 trace: main
+  // grid done 1.7 ms before the rollout kernel, split until 0.6 ms after it, the search after that until 1.9 ms,
+  // profiles/r06w_cfg3_list_crit.txt); the merge still waits for the whole walk.  Its brute-force fallback puts
+  // optimize samples on their own lanes (k_nn_order, nn_order), so explore lanes do not idle while optimize lanes
+  // compute exact keys.
   int* nn_order = nullptr;  // [max_batch]
   int stream_prio = 1;
-  int walk_cu_reserve = 0;  // option "walk_cu_reserve" k = 1..7: lag-2 walk streams kept off k/8 of the CUs
-  int stream_prio_applied = 0;  // the priority setting the current streams were created with
-  bool side_prio_set = false;   // option "side_priority" made the side stream (apply_stream_prio keeps it)
+  bool stream_prio_applied = false;  // the lag-2 streams have stream_prio's priorities (false: all the default one)
   // clrrt_round_prefetch: declared next samples; pf_state 1 = their walk was launched (lists in the
   // set ls[1], merge pending), 2 = merged and swapped in for pf_samples
   std::vector<clrrt_sample> pf_next, pf_samples;
@@ -732,9 +720,6 @@ static void free_all(clrrt_ctx* c) {
   if (c->ev_walk) hipEventDestroy(c->ev_walk);
   if (c->ev_commit) hipEventDestroy(c->ev_commit);
   if (c->side) hipStreamDestroy(c->side);
-  if (c->roll_st) hipStreamDestroy(c->roll_st);
-  if (c->ev_rs0) hipEventDestroy(c->ev_rs0);
-  if (c->ev_rs1) hipEventDestroy(c->ev_rs1);
   if (c->h_totals) hipHostFree(c->h_totals);
   if (c->h_int) hipHostFree(c->h_int);
   if (c->h_bbox) hipHostFree(c->h_bbox);
@@ -1606,7 +1591,6 @@ int clrrt_set_option(clrrt_ctx* c, const char* key, int64_t value) {
     c->nnw_built.n = -1;
     c->nnw.sorted_n = c->nnw_alt.sorted_n = c->nnw3.sorted_n = -1;
   }
-  else if (k == "nn_walk_lpt") c->nnw_lpt = value != 0;  // scheduling only: same lists
   else if (k == "nn_root_seed" || (k == "nn_root_k" && value >= 1 && value <= 64) ||
            (k == "nn_root_scan" && value >= 1 && value <= 32768)) {  // same lists; a kept index has the old marks
     if (k == "nn_root_seed") c->nnw_root_seed = value != 0;
@@ -1619,7 +1603,6 @@ int clrrt_set_option(clrrt_ctx* c, const char* key, int64_t value) {
     c->nnw_built.n = -1;  // the kept index and sort results have the old order
     c->nnw.sorted_n = c->nnw_alt.sorted_n = c->nnw3.sorted_n = -1;
   }
-  else if (k == "nn_walk_lds_floor" && value >= 0 && value <= 65536) c->nnw_lds_floor = (int)value;
   else if (k == "nn_walk_waves" && value >= -1 && value <= 1 << 20) c->nnw_waves = (int)value;
   else if (k == "nn_walk_chunks" && value >= 1 && value <= kWalkMaxChunks) c->nnw_chunks = (int)value;
   else if (k == "nn_walk_max_over" && value >= 1 && value <= kWalkMaxOver) {
@@ -1630,8 +1613,6 @@ int clrrt_set_option(clrrt_ctx* c, const char* key, int64_t value) {
   else if (k == "nn_lag" && (value == 0 || value == 1 || value == 2)) c->nn_lag = (int)value;
   else if (k == "nn_delta_walk") c->nn_delta_walk = value != 0 ? 1 : 0;  // same lists either way
   else if (k == "nn_delta_verify") c->nn_delta_verify = value != 0 ? 1 : 0;  // diagnostics: counters 38 / 39
-  else if (k == "nn_delta_early") c->nn_delta_early = value != 0 ? 1 : 0;  // scheduling only: same lists
-  else if (k == "nn_lane_order") c->nn_lane_order = value != 0 ? 1 : 0;  // scheduling only: same lists
   else if (k == "nn_debug" && value >= 0) c->nn_debug = (int)value;  // diagnostics: changes results
   else if (k == "fail_at_round" && value >= 0 && value < INT_MAX) c->fail_at_round = (int)value;  // fault injection
   else if (k == "fail_after_exchange" && value >= 0 && value < INT_MAX) c->fail_after_exchange = (int)value;
@@ -1659,45 +1640,7 @@ int clrrt_set_option(clrrt_ctx* c, const char* key, int64_t value) {
     if (value > 0 && value < 8) return fail(c, CLRRT_EINVAL, "defer_steps must be 0 or >= 8");
     c->def.T = (int)value;
   }
-  else if (k == "cu_split" && value >= 0 && value <= 7) {
-    HIPC(c, hipStreamSynchronize(c->side));
-    if (c->roll_st) HIPC(c, hipStreamSynchronize(c->roll_st));
-    HIPC(c, hipStreamDestroy(c->side));
-    c->side = nullptr;
-    if (c->roll_st) HIPC(c, hipStreamDestroy(c->roll_st));
-    c->roll_st = nullptr;
-    c->cu_split = (int)value;
-    c->stream_prio_applied = 0;  // the lag-2 streams are re-made for the new split
-    if (value == 0) {
-      HIPC(c, hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking));
-    } else {
-      // CU i goes to the rollouts when i mod 8 < k: k/8 of every run of 8 CU indices
-      const int nw = (c->n_cu + 31) / 32;
-      std::vector<uint32_t> mr(nw, 0u), ms(nw, 0u);
-      for (int i = 0; i < c->n_cu; i++) ((i % 8) < value ? mr : ms)[i / 32] |= 1u << (i % 32);
-      HIPC(c, hipExtStreamCreateWithCUMask(&c->roll_st, (uint32_t)nw, mr.data()));
-      HIPC(c, hipExtStreamCreateWithCUMask(&c->side, (uint32_t)nw, ms.data()));
-      if (!c->ev_rs0) HIPC(c, hipEventCreateWithFlags(&c->ev_rs0, hipEventDisableTiming));
-      if (!c->ev_rs1) HIPC(c, hipEventCreateWithFlags(&c->ev_rs1, hipEventDisableTiming));
-    }
-  }
   else if (k == "stream_prio") c->stream_prio = value != 0;
-  else if (k == "walk_cu_reserve" && value >= 0 && value <= 7) c->walk_cu_reserve = (int)value;
-  else if (k == "side_priority") {  // -1: lower than the main stream's, 0: equal, 1: higher
-    int lo = 0, hi = 0;
-    HIPC(c, hipDeviceGetStreamPriorityRange(&lo, &hi));
-    HIPC(c, hipStreamSynchronize(c->side));
-    HIPC(c, hipStreamDestroy(c->side));
-    const int pr = value > 0 ? hi : value < 0 ? lo : 0;
-    HIPC(c, hipStreamCreateWithPriority(&c->side, hipStreamNonBlocking, pr));
-    c->side_prio_set = true;
-    c->stream_prio_applied = 0;
-    if (value < 0 && c->own_stream) {  // and the main stream gets the highest priority
-      HIPC(c, hipStreamSynchronize(c->stream));
-      HIPC(c, hipStreamDestroy(c->stream));
-      HIPC(c, hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, hi));
-    }
-  }
   else return fail(c, CLRRT_EINVAL, "unknown option or value: " + k);
   return CLRRT_OK;
 }
@@ -1800,11 +1743,9 @@ static int ensure_walk_set(clrrt_ctx* c, WalkBufs& w) {
   w.half_max = c->nnw_half_max;
   w.index_kind = c->nnw_index;
   w.hscale_pct = c->nnw_hscale;
-  w.lpt = c->nnw_lpt;
   w.root_seed = c->nnw_root_seed;
   w.root_k = c->nnw_root_k;
   w.root_scan = c->nnw_root_scan;
-  w.lds_floor = c->nnw_lds_floor;
   w.waves = c->nnw_waves < 0 ? 9 * c->n_cu : c->nnw_waves;
   // the default grid serves batches of >= 4x its waves (cfg2's 4096-sample rounds run 4% faster with one
   // wave per sample: 1.237 vs 1.188 M nodes/s)
@@ -1965,7 +1906,7 @@ static int run_nn(clrrt_ctx* c, int n, KeyId* scratch) {
     c->nnw_built.n = -1;
     HIPC(c, launch_nn_walk(st, cur.d_samples, n, c->nn, (int)c->n_nodes, c->dp, su.fr, su.x0, su.y0, su.x1, su.y1,
                            c->nnw, cur.cand, cur.ckey, cur.ncand, cur.ctie, c->work_ctr + 18, c->nnw_stateless));
-    if (scratch) HIPC(c, launch_nn_exact_only(st, cur.d_samples, n, c->nn, (int)c->n_nodes, c->dp, cur.ctie, scratch,
+    if (scratch) HIPC(c, launch_nn_exact_any(st, cur.d_samples, n, c->nn, (int)c->n_nodes, c->dp, cur.ctie, scratch,
                                               cur.cand, cur.ckey, cur.ncand));
     return CLRRT_OK;
   }
@@ -2217,14 +2158,6 @@ static int eval_samples(clrrt_ctx* c, int n, bool exact, int* L_out, bool have_l
     if (rc != CLRRT_OK) return rc;
   }
   if (during_roll) HIPC(c, hipEventRecord(c->ev_tree, st));
-  // the rollouts' stream: the main one, or (cu_split) their CU-restricted stream, ordered after the
-  // main stream's work so far and joined back right after the launch
-  hipStream_t rst = st;
-  if (c->roll_st) {
-    rst = c->roll_st;
-    HIPC(c, hipEventRecord(c->ev_rs0, st));
-    HIPC(c, hipStreamWaitEvent(rst, c->ev_rs0, 0));
-  }
   const bool persistent = c->roll_persistent && c->dp.n_steps_max > 0;
   const bool deferred = persistent && c->rows_deferred;
   if (!deferred) {  // rows into job slots: replays pending from a deferred round run first
@@ -2243,13 +2176,9 @@ static int eval_samples(clrrt_ctx* c, int n, bool exact, int* L_out, bool have_l
     HIPC(c, hipMemcpyAsync(d.samp + (int64_t)d.slot * B, cur.d_samples, sizeof(clrrt_sample) * n,
                            hipMemcpyDeviceToDevice, st));
     if (d.nd + (int64_t)n > d.vcap) return fail(c, CLRRT_ECAPACITY, "deferred samples exceed the commit buffers");
-    if (rst != st) {  // the copies precede the rollouts' ring writes
-      HIPC(c, hipEventRecord(c->ev_rs0, st));
-      HIPC(c, hipStreamWaitEvent(rst, c->ev_rs0, 0));
-    }
   }
   {
-    KTimer kt(c, 1, rst);
+    KTimer kt(c, 1, st);
     RollArgs a = roll_args(c, n * CAND_K);
     a.res = c->res_spec;
     a.res_gb = c->res_gb;
@@ -2272,7 +2201,6 @@ static int eval_samples(clrrt_ctx* c, int n, bool exact, int* L_out, bool have_l
     const int64_t nt = c->n_nodes;
     const int eighths = nt < 300000 ? 7 : nt < 700000 ? 5 : nt < 1100000 ? 4 : 2;
     const int blocks = c->roll_blocks > 0 ? std::min(c->roll_blocks, 4 * c->n_cu)
-                       : c->cu_split > 0  ? std::max(1, (c->cu_split * c->n_cu) / 8)
                                           : std::max(1, (eighths * c->n_cu) / 8);
     a.coop_enable = c->roll_coop;
     a.lanes_per_wave = c->roll_lanes > 0 ? c->roll_lanes : c->roll_spread ? 0 : 64;
@@ -2286,7 +2214,7 @@ static int eval_samples(clrrt_ctx* c, int n, bool exact, int* L_out, bool have_l
       if (!dbg_host) HIPC(c, hipHostMalloc((void**)&dbg_host, sizeof(unsigned long long) * 8 * 4096, hipHostMallocMapped));
       memset(dbg_host, 0, sizeof(unsigned long long) * 8 * 4096);
       HIPC(c, hipHostGetDevicePointer((void**)&a.dbg, dbg_host, 0));
-      HIPC(c, hipStreamSynchronize(rst));
+      HIPC(c, hipStreamSynchronize(st));
       fprintf(stderr, "[dbg] pre-rollout work done (n %d, nrep %d, ncarry %d)\n", n, a.nrep, a.ncarry);
     }
     if (persistent && defer) {
@@ -2298,16 +2226,16 @@ static int eval_samples(clrrt_ctx* c, int n, bool exact, int* L_out, bool have_l
       f.add(c->def.best + a.sbase, n, 0x7f7f7f7f);
       f.add(c->def.d_cnt + 2, 1, 0);
       f.add((int*)c->totals, 16, 0);
-      HIPC(c, launch_fill_ints(rst, f));
+      HIPC(c, launch_fill_ints(st, f));
       c->totals_zeroed = true;
-      HIPC(c, launch_rollout_persistent(rst, a, n, c->roll_q, c->def.best, blocks, true));
+      HIPC(c, launch_rollout_persistent(st, a, n, c->roll_q, c->def.best, blocks, true));
     } else if (persistent)
-      HIPC(c, launch_rollout_persistent(rst, a, n, c->roll_q, defer ? c->def.best : c->roll_best, blocks));
+      HIPC(c, launch_rollout_persistent(st, a, n, c->roll_q, defer ? c->def.best : c->roll_best, blocks));
     else
-      HIPC(c, launch_rollout(rst, SRC_SPEC, a));
+      HIPC(c, launch_rollout(st, SRC_SPEC, a));
     if (c->debug_sync) {
       const auto t0 = std::chrono::steady_clock::now();
-      while (hipStreamQuery(rst) == hipErrorNotReady) {
+      while (hipStreamQuery(st) == hipErrorNotReady) {
         if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > 10.0) {
           fprintf(stderr, "[dbg] rollout kernel not done after 10 s; waves (iterations, busy, parked, qdone|first "
                           "busy lane, j|pass, steps|chain, wp|N, t):\n");
@@ -2330,14 +2258,10 @@ static int eval_samples(clrrt_ctx* c, int n, bool exact, int* L_out, bool have_l
           abort();
         }
       }
-      fprintf(stderr, "[dbg] rollout kernel done: %s\n", hipGetErrorString(hipStreamQuery(rst)));
+      fprintf(stderr, "[dbg] rollout kernel done: %s\n", hipGetErrorString(hipStreamQuery(st)));
     }
     if (deferred) c->rep_n = 0;
     c->eval_deferred = deferred;
-  }
-  if (c->roll_st) {
-    HIPC(c, hipEventRecord(c->ev_rs1, rst));
-    HIPC(c, hipStreamWaitEvent(st, c->ev_rs1, 0));
   }
   if (during_roll) {  // queued behind the rollout kernel, whose persistent blocks take the CUs first
     int rc = during_roll();
@@ -3038,7 +2962,7 @@ static int commit_round(clrrt_ctx* c, int nn, double elapsed_ms, int* n_app) {
 // the next rounds are known ahead.  The walk search of round r+2's samples runs over the tree T_r (the
 // tree round r's rollouts start from) on a side stream, beside rounds r and r+1; after round r+1's
 // commit the nodes those two rounds appended, [|T_r|, |T_{r+2}|), are searched and merged in
-// (launch_nn_delta: every appended id is larger than every older one, so the merged lists equal a search
+// (launch_nn_delta_merge: every appended id is larger than every older one, so the merged lists equal a search
 // over T_{r+2}).  A search thus has two rounds' time instead of one.  Three list sets rotate (this
 // round's, round r+1's being merged, round r+2's being searched), three walk index sets (the one being
 // searched by round r+1's walk, the one by round r+2's, the one being built for the next), and two side
@@ -3059,15 +2983,7 @@ static int lag_alloc(clrrt_ctx* c) {
     for (hipEvent_t* e : {&s.ev, &s.evw, &s.evm}) HIPC(c, hipEventCreateWithFlags(e, hipEventDisableTiming));
     HIPC(c, dalloc(&s.wseed, B));
   }
-  if (c->cu_split > 0) {  // the same CUs as the side stream
-    const int nw = (c->n_cu + 31) / 32;
-    std::vector<uint32_t> ms(nw, 0u);
-    for (int i = 0; i < c->n_cu; i++)
-      if ((i % 8) >= c->cu_split) ms[i / 32] |= 1u << (i % 32);
-    HIPC(c, hipExtStreamCreateWithCUMask(&c->side2, (uint32_t)nw, ms.data()));
-  } else {
-    HIPC(c, hipStreamCreateWithFlags(&c->side2, hipStreamNonBlocking));
-  }
+  HIPC(c, hipStreamCreateWithFlags(&c->side2, hipStreamNonBlocking));
   HIPC(c, hipStreamCreateWithFlags(&c->mst, hipStreamNonBlocking));
   HIPC(c, dalloc(&c->nn_order, B));
   return CLRRT_OK;
@@ -3109,13 +3025,11 @@ static int alloc_walk_delta(clrrt_ctx* c) {
 }
 
 // Stream priorities of the lag-2 rounds (option "stream_prio"): main and merge streams highest, the walk
-// streams lowest (1), or all equal (0).  CU-masked streams (cu_split) keep theirs.  Scheduling only.
+// streams lowest (1), or all equal (0).  Scheduling only.
 static int apply_stream_prio(clrrt_ctx* c) {
-  const int want = (c->stream_prio ? 1 : 2) + 4 * c->walk_cu_reserve;  // 2: equal priorities
-  if (c->stream_prio_applied == want || c->cu_split > 0) return CLRRT_OK;
+  if (c->stream_prio_applied == (c->stream_prio != 0)) return CLRRT_OK;
   int lo = 0, hi = 0;
   HIPC(c, hipDeviceGetStreamPriorityRange(&lo, &hi));
-  // the priorities follow stream_prio alone (the CU reservation only masks the walk streams)
   const int p_hi = c->stream_prio ? hi : 0, p_lo = c->stream_prio ? lo : 0;
   HIPC(c, hipDeviceSynchronize());
   auto remake = [&](hipStream_t& st, int pr) -> int {
@@ -3124,22 +3038,10 @@ static int apply_stream_prio(clrrt_ctx* c) {
     return CLRRT_OK;
   };
   int rc;
-  if (c->walk_cu_reserve > 0) {  // the walk streams on the CUs with (cu % 8) >= k (no priority on CU-masked streams)
-    const int nw = (c->n_cu + 31) / 32;
-    std::vector<uint32_t> ms(nw, 0u);
-    for (int i = 0; i < c->n_cu; i++)
-      if ((i % 8) >= c->walk_cu_reserve) ms[i / 32] |= 1u << (i % 32);
-    for (hipStream_t* st : {&c->side, &c->side2}) {
-      if (*st) HIPC(c, hipStreamDestroy(*st));
-      HIPC(c, hipExtStreamCreateWithCUMask(st, (uint32_t)nw, ms.data()));
-    }
-    if ((rc = remake(c->mst, p_hi)) != CLRRT_OK) return rc;
-  } else if ((!c->side_prio_set && (rc = remake(c->side, p_lo)) != CLRRT_OK) ||
-             (rc = remake(c->side2, p_lo)) != CLRRT_OK || (rc = remake(c->mst, p_hi)) != CLRRT_OK) {
-    return rc;  // (an explicit side_priority keeps the side stream it made)
-  }
-  if (c->own_stream && (rc = remake(c->stream, p_hi)) != CLRRT_OK) return rc;
-  c->stream_prio_applied = want;
+  if ((rc = remake(c->side, p_lo)) != CLRRT_OK || (rc = remake(c->side2, p_lo)) != CLRRT_OK ||
+      (rc = remake(c->mst, p_hi)) != CLRRT_OK || (c->own_stream && (rc = remake(c->stream, p_hi)) != CLRRT_OK))
+    return rc;
+  c->stream_prio_applied = c->stream_prio != 0;
   return CLRRT_OK;
 }
 
@@ -3276,7 +3178,6 @@ static int expand_lag2(clrrt_ctx* c, clrrt_rng* rng, int64_t n_iters, double bud
   LagSlot A, B;
   A.set = c->ls[1];
   B.set = c->ls[2];
-  const bool early = c->nn_delta_early != 0;
   // The appended-node search walks its range's own index (nn_delta_walk) from one tile of appended nodes on: a range
   // inside one tile has a single bound, so the walk would prefilter every record as k_nn_partial does, behind three
   // more launches (a range above the set's capacity takes the brute force too).
@@ -3312,8 +3213,8 @@ static int expand_lag2(clrrt_ctx* c, clrrt_rng* rng, int64_t n_iters, double bud
     c->nn_super_bounds += (int64_t)n * walk_super_count(c->n_nodes);
     {
       KTimer kt(c, 0, s), kt3(c, 3, s);
-      W[k]->seed_out = early ? l.wseed : nullptr;
-      W[k]->ev_main = early ? l.evm : nullptr;
+      W[k]->seed_out = l.wseed;
+      W[k]->ev_main = l.evm;
       const hipError_t ew = launch_nn_walk_search(s, l.d_samples, n, c->nn, (int)c->n_nodes, c->dp, su.fr, su.x0, su.y0,
                                                   su.x1, su.y1, *W[k], l.cand, l.ckey, l.ncand, l.ctie, c->work_ctr + 18,
                                                   c->nnw_stateless);
@@ -3406,16 +3307,16 @@ static int expand_lag2(clrrt_ctx* c, clrrt_rng* rng, int64_t n_iters, double bud
     if ((r = commit_round(c, nn, x.ms_since(x.t0), &n_app)) != CLRRT_OK) return r;
     if (c->fail_in_round > 0 && --c->fail_in_round == 0)
       return fail(c, CLRRT_ECAPACITY, "injected failure (option fail_in_round)");
-    // slot A: merge the nodes appended since its walk's tree.  On the merge stream, behind the commit and -- early --
-    // slot A's main walk grid (caps from its k_walk_seed, beside the walk's overflow split) or the whole walk (caps from
-    // its list); the merge behind the whole walk.  The search walks the range's own index (launch_nn_delta_walk) where
-    // the walk is served (region, tree size) and the range is neither tiny nor beyond the set; else the brute force.
+    // slot A: merge the nodes appended since its walk's tree.  On the merge stream, behind the commit and slot A's main
+    // walk grid (caps from its k_walk_seed, beside the walk's overflow split); the merge behind the whole walk.  The
+    // search walks the range's own index (launch_nn_delta_walk) where the walk is served (region, tree size) and the
+    // range is neither tiny nor beyond the set; else the brute force.
     if (A.n > 0) {
       ListSet& a = *A.set;
       HIPC(c, hipEventRecord(c->ev_commit, c->stream));
       hipStream_t s = c->mst;
       HIPC(c, hipStreamWaitEvent(s, c->ev_commit, 0));
-      HIPC(c, hipStreamWaitEvent(s, early ? a.evm : a.evw, 0));
+      HIPC(c, hipStreamWaitEvent(s, a.evm, 0));
       const int64_t first = A.tree_n, cnt = c->n_nodes - A.tree_n;
       const NnSetup su2 = nn_setup(c);
       const bool dwalk = delta_walk && su2.region_ok && c->n_nodes >= c->nnw_min_nodes && cnt >= delta_walk_min &&
@@ -3425,32 +3326,26 @@ static int expand_lag2(clrrt_ctx* c, clrrt_rng* rng, int64_t n_iters, double bud
       if (cnt > 0) c->nn_bf_keys += (int64_t)A.n * cnt;
       if (cnt > 0 && dwalk) {
         KTimer kt(c, 0, s);
-        float* seed = early ? a.wseed : c->nn_seed;
         const bool verify = c->nn_delta_verify && c->vseed;
         HIPC(c, launch_nn_delta_walk(s, a.d_samples, A.n, c->nn, (int)first, (int)cnt, c->dp, su2.fr, su2.x0, su2.y0,
-                                     su2.x1, su2.y1, c->nnw_d, c->pk, c->pi, a.ckey, a.ncand, seed, early,
+                                     su2.x1, su2.y1, c->nnw_d, c->pk, c->pi, a.wseed,
                                      verify ? c->work_ctr + 40 : nullptr));
         nch = 1;
         id0 = 0;
         if (verify) {  // the brute force over the same range and caps, and the two list sets compared
           int vch = 0;
-          HIPC(c, hipMemcpyAsync(c->vseed, seed, sizeof(float) * A.n, hipMemcpyDeviceToDevice, s));
+          HIPC(c, hipMemcpyAsync(c->vseed, a.wseed, sizeof(float) * A.n, hipMemcpyDeviceToDevice, s));
           HIPC(c, launch_nn_delta_partial(s, a.d_samples, A.n, c->nn, (int)first, (int)cnt, c->dp, su2.fr, c->vpk,
                                           c->vpi, max_chunks, nullptr, nullptr, c->vseed, true, nullptr, &vch,
                                           c->work_ctr + 52));
           HIPC(c, launch_nn_delta_compare(s, A.n, vch, (int)first, c->vpk, c->vpi, c->pk, c->pi, c->work_ctr + 38));
         }
-      } else if (cnt > 0 && early) {
-        KTimer kt(c, 0, s);
-        HIPC(c, launch_nn_delta_partial(s, a.d_samples, A.n, c->nn, (int)first, (int)cnt, c->dp, su2.fr, c->pk, c->pi,
-                                        max_chunks, nullptr, nullptr, a.wseed, true,
-                                        c->nn_lane_order ? c->nn_order : nullptr, &nch));
       } else if (cnt > 0) {
         KTimer kt(c, 0, s);
-        HIPC(c, launch_nn_delta(s, a.d_samples, A.n, c->nn, (int)first, (int)cnt, c->dp, su2.fr, c->pk, c->pi,
-                                max_chunks, a.cand, a.ckey, a.ncand, a.ctie, c->nn_seed));
+        HIPC(c, launch_nn_delta_partial(s, a.d_samples, A.n, c->nn, (int)first, (int)cnt, c->dp, su2.fr, c->pk, c->pi,
+                                        max_chunks, nullptr, nullptr, a.wseed, true, c->nn_order, &nch));
       }
-      if (early) HIPC(c, hipStreamWaitEvent(s, a.evw, 0));
+      HIPC(c, hipStreamWaitEvent(s, a.evw, 0));
       if (nch > 0) {
         KTimer kt(c, 0, s);
         HIPC(c, launch_nn_delta_merge(s, A.n, nch, c->dp, c->pk, c->pi, id0, a.cand, a.ckey, a.ncand, a.ctie));

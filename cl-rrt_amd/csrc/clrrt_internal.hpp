@@ -218,10 +218,9 @@ struct WalkBufs {
   WalkTile *tiles, *supers;
   // overflow of the walk: a sample whose walk passes the budget (tiles visited / exact keys) hands
   // its search to nch waves over interleaved super-tile subsets with the list's 11th entry as the
-  // bound, then a merge wave (k_walk_split / k_walk_merge); budget 0 = off
+  // bound, then a merge wave (k_walk_search_split / k_walk_merge); budget 0 = off
   int bud_tiles, bud_ex, max_over, nch;
   int half_max = 4096;  // fp16 LDS bounds up to this many super-tiles, coded bytes (+ inside bracket) beyond
-  int lds_floor = 0;    // bytes of LDS each walk wave reserves at least (caps the walk's waves per CU)
   int waves = 0;        // > 0: a persistent walk grid of this many waves (samples from per-XCD counters)
   int waves_min_batch = 0;  // ... used for batches of at least this many samples
   // place order of the index (option "nn_walk_index"): 0 = ang_par sector, then the 2D Morton code of the
@@ -242,7 +241,6 @@ struct WalkBufs {
   int root_seed = 1;       // 0: no roster, no root-class marks in HEAD (the walk as it was)
   int root_k = 64;         // roster entries (<= 64: one per lane)
   int root_scan = 16384;   // ids [0, min(N, root_scan)) are scanned for them (<= 32768)
-  int lpt = 0;          // the persistent grid's eighths: optimize samples first (k_walk_lpt, option nn_walk_lpt)
   // set by the caller around one launch_nn_walk_search: [B] key caps for the appended-node search written right after
   // the main grid (k_walk_seed), and an event recorded there (before the overflow split); null: neither
   float* seed_out = nullptr;
@@ -289,14 +287,13 @@ hipError_t launch_nn_delta(hipStream_t st, const clrrt_sample* S, int B, const N
                            float* ckey, int* ncand, int* ctie, float* seed);
 // The appended-node search as a walk (clrrt_nnwalk.hip): an index of nodes [first, first + count) alone in w (a set
 // of walk_delta_cap nodes; keys, sort, one fused index kernel) and one wave per sample walking it from the sample's
-// key cap in seed[B] (seeded: already there, k_walk_seed's; else taken from the older list ckey / ncand first).  The
+// key cap in seed[B] (k_walk_seed's, written after the older list's main walk grid).  The
 // lists go to pk / pi, NN_K entries per sample with the nodes' own ids: launch_nn_delta_merge with nchunks 1, id0 0.
 // (x0, y0, x1, y1): the Morton frame of nn_setup at this commit, fr its float frame.
 int64_t walk_delta_cap(int64_t max_nodes, int64_t max_batch);
 hipError_t launch_nn_delta_walk(hipStream_t st, const clrrt_sample* S, int B, const NnRec* nodes, int first, int count,
                                 const DevParams& p, const NnFrame& fr, double x0, double y0, double x1, double y1,
-                                WalkBufs& w, float* pk, int* pi, const float* ckey, const int* ncand, float* seed,
-                                bool seeded, unsigned long long* stats);
+                                WalkBufs& w, float* pk, int* pi, float* seed, unsigned long long* stats);
 // Option nn_delta_verify: the brute force's chunk lists (pk / pi, ids relative to id0) against the walk's lists (wk /
 // wi) of the same search; out[0] += samples compared, out[1] += samples whose NN_K (key bits, id) pairs differ.
 hipError_t launch_nn_delta_compare(hipStream_t st, int B, int nchunks, int id0, const float* pk, const int* pi,
@@ -324,9 +321,9 @@ hipError_t launch_nn(hipStream_t st, const clrrt_sample* S, int B, const NnRec* 
                      const DevParams& p, float* pk, int* pi, int* cand, float* ckey, int* ncand, int* ctie,
                      int max_chunks, KeyId* exact_scratch, float* seed, unsigned long long* stats, const NnFrame& fr);
 // EXACT mode after a search that filled ctie: std::sort replay for the tied samples.
-hipError_t launch_nn_exact_only(hipStream_t st, const clrrt_sample* S, int B, const NnRec* nodes, int N,
-                                const DevParams& p, const int* ctie, KeyId* scratch, int* cand, float* ckey,
-                                int* ncand);
+hipError_t launch_nn_exact_any(hipStream_t st, const clrrt_sample* S, int B, const NnRec* nodes, int N,
+                               const DevParams& p, const int* ctie, KeyId* scratch, int* cand, float* ckey,
+                               int* ncand);
 hipError_t launch_rollout(hipStream_t st, int src, const RollArgs& a);
 // EXACT-mode lists of a tree of at most nn_exact_small_max() nodes, one wave per sample (k_nn_exact_fused:
 // keys, list, tie flag and the std::sort replay of tied samples in one kernel)

@@ -5,7 +5,7 @@
 //                               node loads, per-lane top-K in registers, Euclidean prune (key >= |q|)
 //   k_rollout                 : closed-loop rollouts (Simulation, simulation.cpp:36-143), one lane per
 //                               rollout job; obstacle bounding circles staged in LDS
-//   k_select / k_gb_select    : first successful candidate per sample (expandTree :150-160), goal-bias
+//   k_select                  : first successful candidate per sample (expandTree :150-160), goal-bias
 //                               gate (feasibleGoalBias :292-315) and node construction (:156,170)
 //   k_conflict                : EXACT mode — does a node appended earlier in the round reorder a
 //                               later sample's candidate list?
@@ -757,9 +757,9 @@ __global__ void __launch_bounds__(64) k_nn_exact_fused(const clrrt_sample* __res
 
 // EXACT-mode tie replay for the samples with ctie set: in LDS when the tree fits, else one lane per
 // sample over the global scratch.
-static hipError_t launch_nn_exact_any(hipStream_t st, const clrrt_sample* S, int B, const NnRec* nodes, int N,
-                                      const DevParams& p, const int* ctie, KeyId* scratch, int* cand, float* ckey,
-                                      int* ncand) {
+hipError_t launch_nn_exact_any(hipStream_t st, const clrrt_sample* S, int B, const NnRec* nodes, int N,
+                               const DevParams& p, const int* ctie, KeyId* scratch, int* cand, float* ckey,
+                               int* ncand) {
   if (N <= NN_EXACT_LDS_MAX) {
     const size_t lds = sizeof(KeyId) * (size_t)N + sizeof(int2) * (size_t)(N / 2 + 64);
     if (lds > 64 * 1024) {
@@ -3056,6 +3056,20 @@ static hipError_t launch_nn_brute(hipStream_t st, const clrrt_sample* S, int B, 
                                   float* ckey, int* ncand, int* ctie, int max_chunks, const float* seed = nullptr,
                                   unsigned long long* tstat = nullptr);
 
+// k_nn_partial's split of `count` nodes for `groups` sample groups: as many chunks as make >= 2048 blocks (at most
+// max_chunks), each a multiple of 256 nodes, so tiles of 256 nodes never straddle chunks.
+struct NnChunks {
+  int nchunks, chunk;
+};
+static NnChunks nn_chunks(int count, int groups, int max_chunks) {
+  int nchunks = (count + 255) / 256;
+  const int want = max(1, 2048 / max(1, groups));
+  nchunks = max(1, min(nchunks, min(want, max_chunks)));
+  int chunk = (count + nchunks - 1) / nchunks;
+  chunk = (chunk + 255) & ~255;
+  return {(count + chunk - 1) / chunk, chunk};
+}
+
 hipError_t launch_nn(hipStream_t st, const clrrt_sample* S, int B, const NnRec* nodes, int N,
                      const DevParams& p, float* pk, int* pi, int* cand, float* ckey, int* ncand, int* ctie,
                      int max_chunks, KeyId* exact_scratch, float* seed, unsigned long long* stats, const NnFrame& fr) {
@@ -3130,12 +3144,7 @@ hipError_t launch_nn_delta(hipStream_t st, const clrrt_sample* S, int B, const N
   // (the seed / merge kernels and the index build run one-wave blocks: they run beside the lag-2 walk, whose
   // waves fill the CUs and free one slot at a time; priorities order dispatch but do not preempt)
   const int groups = (B + CLRRT_PATH_BLK - 1) / CLRRT_PATH_BLK;
-  int nchunks = (count + 255) / 256;
-  const int want = max(1, 2048 / max(1, groups));
-  nchunks = max(1, min(nchunks, min(want, max_chunks)));
-  int chunk = (count + nchunks - 1) / nchunks;
-  chunk = (chunk + 255) & ~255;
-  nchunks = (count + chunk - 1) / chunk;
+  const auto [nchunks, chunk] = nn_chunks(count, groups, max_chunks);
   hipLaunchKernelGGL(k_nn_delta_seed, dim3((B + 63) / 64), dim3(64), 0, st, B, p.sort_limit, ckey, ncand, seed);
   LAUNCH_CHECK();
   hipLaunchKernelGGL(k_nn_partial, dim3(groups, nchunks), dim3(CLRRT_PATH_BLK), 0, st, S, B, nodes + first, count, chunk,
@@ -3165,12 +3174,7 @@ hipError_t launch_nn_delta_partial(hipStream_t st, const clrrt_sample* S, int B,
     sord = order;
   }
   const int groups = (B + CLRRT_PATH_BLK - 1) / CLRRT_PATH_BLK;
-  int nchunks = (count + 255) / 256;
-  const int want = max(1, 2048 / max(1, groups));
-  nchunks = max(1, min(nchunks, min(want, max_chunks)));
-  int chunk = (count + nchunks - 1) / nchunks;
-  chunk = (chunk + 255) & ~255;
-  nchunks = (count + chunk - 1) / chunk;
+  const auto [nchunks, chunk] = nn_chunks(count, groups, max_chunks);
   if (!seeded) {  // (seeded: the caller's caps, e.g. k_walk_seed's)
     hipLaunchKernelGGL(k_nn_delta_seed, dim3((B + 63) / 64), dim3(64), 0, st, B, ckey ? p.sort_limit : 0, ckey, ncand,
                        gcap);
@@ -3199,26 +3203,13 @@ hipError_t launch_nn_delta_compare(hipStream_t st, int B, int nchunks, int id0, 
   return hipSuccess;
 }
 
-hipError_t launch_nn_exact_only(hipStream_t st, const clrrt_sample* S, int B, const NnRec* nodes, int N,
-                                const DevParams& p, const int* ctie, KeyId* scratch, int* cand, float* ckey,
-                                int* ncand) {
-  return launch_nn_exact_any(st, S, B, nodes, N, p, ctie, scratch, cand, ckey, ncand);
-}
-
 static hipError_t launch_nn_brute(hipStream_t st, const clrrt_sample* S, int B, const NnRec* nodes, int N,
                                   const DevParams& p, const NnFrame& fr, float* pk, int* pi, int* cand,
                                   float* ckey, int* ncand, int* ctie, int max_chunks, const float* seed,
                                   unsigned long long* tstat) {
-  int threads = 256;
-  int groups = (B + 255) / 256;
-  int nchunks = (N + 255) / 256;
-  int want = max(1, 2048 / max(1, groups));  // aim for >= 2048 blocks of 4 waves
-  nchunks = max(1, min(nchunks, min(want, max_chunks)));
-
-  int chunk = (N + nchunks - 1) / nchunks;
-  chunk = (chunk + 255) & ~255;  // tiles of 256 nodes never straddle chunks
-  nchunks = (N + chunk - 1) / chunk;
-  hipLaunchKernelGGL(k_nn_partial, dim3(groups, nchunks), dim3(threads), 0, st, S, B, nodes, N, chunk, nchunks,
+  const int groups = (B + 255) / 256;
+  const auto [nchunks, chunk] = nn_chunks(N, groups, max_chunks);
+  hipLaunchKernelGGL(k_nn_partial, dim3(groups, nchunks), dim3(256), 0, st, S, B, nodes, N, chunk, nchunks,
                      p, fr, pk, pi, seed, tstat, nullptr);
   LAUNCH_CHECK();
   hipLaunchKernelGGL(k_nn_merge, dim3((B + 255) / 256), dim3(256), 0, st, B, nchunks, p.sort_limit, pk, pi,

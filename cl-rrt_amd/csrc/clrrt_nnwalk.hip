@@ -219,40 +219,6 @@ __global__ void k_walk_skeys(const clrrt_sample* __restrict__ S, int B, double x
   vals[i] = i;
 }
 
-// Longest-first order inside each XCD's eighth of the place-ordered samples (option nn_walk_lpt): the persistent
-// walk hands an eighth's samples out in order, so its optimize samples (several times an explore sample's exact
-// keys, profiles/r06g_walk_audit.txt) go first and the cheap explore samples fill the end; each class keeps its
-// place order (a stable partition, one 1024-thread block per eighth).  Scheduling only: every list is the same.
-__global__ void __launch_bounds__(1024) k_walk_lpt(const clrrt_sample* __restrict__ S, int B,
-                                                   const int* __restrict__ sorder, int* __restrict__ out) {
-  __shared__ int part[1024];
-  const int per = (B + 7) >> 3;
-  const int base = (int)blockIdx.x * per;
-  const int n = min(per, B - base);
-  if (n <= 0) return;
-  const int t = threadIdx.x;
-  const int ipt = (n + 1023) >> 10;
-  const int i0 = min(n, t * ipt), i1 = min(n, i0 + ipt);
-  int c = 0;
-  for (int i = i0; i < i1; i++) c += S[sorder[base + i]].explore == 0;
-  part[t] = c;
-  __syncthreads();
-  for (int d = 1; d < 1024; d <<= 1) {  // inclusive scan of the optimize counts
-    const int v = t >= d ? part[t - d] : 0;
-    __syncthreads();
-    part[t] += v;
-    __syncthreads();
-  }
-  const int total = part[1023];
-  int po = part[t] - c;  // optimize samples before this thread's items
-  int pe = i0 - po;      // explore samples before them
-  for (int i = i0; i < i1; i++) {
-    const int v = sorder[base + i];
-    if (S[v].explore == 0) out[base + po++] = v;
-    else out[base + total + pe++] = v;
-  }
-}
-
 // Per tile: (run head, smallest id) when all 32 records lie in one run of equal key inputs (HEAD is the
 // run's first record: equal at the tile's ends), else (-1, -1).
 __global__ void k_walk_trun(const int* __restrict__ HEAD, const int* __restrict__ ID, int ntiles,
@@ -409,7 +375,7 @@ __global__ void __launch_bounds__(256) k_walk_tiles(const float4* __restrict__ P
   walk_tile_bounds(P, Q, CE, ID, t, size, slack, Rx, Ry, lane, out);
 }
 
-// The index of a short node range in ONE launch behind its sort (launch_nn_walk_build_range): block b gathers the
+// The index of a short node range in ONE launch behind its sort (launch_nn_delta_walk): block b gathers the
 // 1024 records of super-tile b from the sorted ids (k_walk_gather's records; ID holds the nodes' own ids), scans the
 // run markers into HEAD, and writes the tiles' run records (k_walk_trun), the 32 tile bounds and the super-tile's
 // (walk_tile_bounds).  Runs of equal records are cut at super-tile boundaries: a run's parts are runs too, so the
@@ -1908,59 +1874,42 @@ hipError_t launch_nn_walk_search(hipStream_t st, const clrrt_sample* S, int B, c
   // none, then one coded byte (+ the inside-circle key bracket: on such trees exact keys dominate)
   const int fmt = nsup <= 1280 && !stateless ? WALK_FMT_STATE : (nsup <= w.half_max ? WALK_FMT_HALF : WALK_FMT_CODED);
   const bool brk = fmt == WALK_FMT_CODED;
-  // (a floor on it caps the walk's waves per CU, leaving room for the main stream's kernels beside it)
-  const size_t lds = std::max<size_t>((size_t)w.lds_floor,
-                                      (fmt == WALK_FMT_STATE ? 2 * sizeof(float)
-                                       : fmt == WALK_FMT_HALF ? (WALK_HALF_SUPER ? 2 : 1) * sizeof(__half)
-                                                              : 1) *
-                                          (size_t)nsup);
-  const bool pers_k = w.waves > 0 && w.wctr && B >= w.waves_min_batch;
-  const void* kfn =
-      fmt == WALK_FMT_STATE ? (pers_k ? (const void*)&k_walk_search<WALK_FMT_STATE, false, false, true>
-                                      : (const void*)&k_walk_search<WALK_FMT_STATE, false, false, false>)
-      : fmt == WALK_FMT_HALF ? (pers_k ? (const void*)&k_walk_search<WALK_FMT_HALF, false, false, true>
-                                       : (const void*)&k_walk_search<WALK_FMT_HALF, false, false, false>)
-                             : (pers_k ? (const void*)&k_walk_search<WALK_FMT_CODED, false, true, true>
-                                       : (const void*)&k_walk_search<WALK_FMT_CODED, false, true, false>);
-  if (lds > 64 * 1024) {
-    e = hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
+  const size_t lds = (fmt == WALK_FMT_STATE ? 2 * sizeof(float)
+                      : fmt == WALK_FMT_HALF ? (WALK_HALF_SUPER ? 2 : 1) * sizeof(__half)
+                                             : 1) *
+                     (size_t)nsup;
+  // persistent waves (option nn_walk_waves): a fixed grid taking samples from per-XCD counters
+  const bool pers = w.waves > 0 && w.wctr && B >= w.waves_min_batch;
   const bool split = (w.bud_tiles > 0 || w.bud_ex > 0) && w.max_over > 0 && w.nch > 0 && w.ovf_n;
-  const bool pers_z = w.waves > 0 && w.wctr && B >= w.waves_min_batch;
   // samples in place order (radix sort of their Morton keys; the node sort's buffers are free again); the
   // key kernel also resets the overflow count and the persistent grid's counters
   hipLaunchKernelGGL(k_walk_skeys, dim3((B + 255) / 256), dim3(256), 0, st, S, B, x0, y0, scale, w.keys, w.vals,
-                     split ? w.ovf_n : nullptr, pers_z ? w.wctr : nullptr);
+                     split ? w.ovf_n : nullptr, pers ? w.wctr : nullptr);
   LAUNCH_CHECK3();
   bytes = w.tmp_bytes;
   e = hipcub::DeviceRadixSort::SortPairs(w.tmp, bytes, w.keys, w.keys2, w.vals, w.sorder, B, 0, 32, st);
   if (e != hipSuccess) return e;
   const int* sorder = w.sorder;
-  if (w.lpt && B >= 8) {  // (the sorted keys in keys2 are not read again: its 2 M words hold the new order)
-    hipLaunchKernelGGL(k_walk_lpt, dim3(8), dim3(1024), 0, st, S, B, (const int*)w.sorder, (int*)w.keys2);
-    LAUNCH_CHECK3();
-    sorder = (const int*)w.keys2;
-  }
   const int bt = split ? w.bud_tiles : 0, be = split ? w.bud_ex : 0;
-  // persistent waves (option nn_walk_waves): a fixed grid taking samples from per-XCD counters
-  const bool pers = pers_k;
   const int grid = pers ? std::min(((B + 7) >> 3) * 8, std::max(8, w.waves & ~7)) : ((B + 7) >> 3) * 8;
   int* wctr = pers ? w.wctr : nullptr;
-#define WALK_LAUNCH1(F, BK, PS)                                                                                  \
-  hipLaunchKernelGGL((k_walk_search<F, false, BK, PS>), dim3(grid), dim3(64), lds, st, S, B, nodes, w.P,          \
-                     w.Q, w.CE, w.ID, w.HEAD, w.trun, w.tiles, ntiles, w.supers, nsup, p, fr, cand, ckey, ncand, ctie,  \
-                     sorder, stats, bt, be, w.ovf_n, w.ovf, w.max_over, w.nch, w.pk, w.pi, nsup, wctr, (const int*)w.roster)
-#define WALK_LAUNCH(F, BK)            \
-  do {                                \
-    if (pers) WALK_LAUNCH1(F, BK, true);  \
-    else WALK_LAUNCH1(F, BK, false);  \
-  } while (0)
-  if (fmt == WALK_FMT_STATE) WALK_LAUNCH(WALK_FMT_STATE, false);
-  else if (fmt == WALK_FMT_HALF) WALK_LAUNCH(WALK_FMT_HALF, false);
-  else WALK_LAUNCH(WALK_FMT_CODED, true);
-#undef WALK_LAUNCH
-#undef WALK_LAUNCH1
+  // one instantiation for the LDS attribute and the launch
+  auto run = [&](auto F, auto BK, auto PS) -> hipError_t {
+    auto* kfn = &k_walk_search<decltype(F)::value, false, decltype(BK)::value, decltype(PS)::value>;
+    if (lds > 64 * 1024) {
+      const hipError_t ea = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      if (ea != hipSuccess) return ea;
+    }
+    hipLaunchKernelGGL(kfn, dim3(grid), dim3(64), lds, st, S, B, nodes, w.P, w.Q, w.CE, w.ID, w.HEAD, w.trun, w.tiles,
+                       ntiles, w.supers, nsup, p, fr, cand, ckey, ncand, ctie, sorder, stats, bt, be, w.ovf_n, w.ovf,
+                       w.max_over, w.nch, w.pk, w.pi, nsup, wctr, (const int*)w.roster);
+    return hipSuccess;
+  };
+  auto run_fmt = [&](auto F, auto BK) { return pers ? run(F, BK, std::true_type{}) : run(F, BK, std::false_type{}); };
+  e = fmt == WALK_FMT_STATE  ? run_fmt(std::integral_constant<int, WALK_FMT_STATE>{}, std::false_type{})
+      : fmt == WALK_FMT_HALF ? run_fmt(std::integral_constant<int, WALK_FMT_HALF>{}, std::false_type{})
+                             : run_fmt(std::integral_constant<int, WALK_FMT_CODED>{}, std::true_type{});
+  if (e != hipSuccess) return e;
   LAUNCH_CHECK3();
   if (w.seed_out) {  // the appended-node search's caps, before the split (its records are claimed by now)
     hipLaunchKernelGGL(k_walk_seed, dim3((B + 63) / 64), dim3(64), 0, st, B, p.sort_limit, (const float*)ckey,
@@ -2036,8 +1985,7 @@ int64_t walk_delta_cap(int64_t max_nodes, int64_t max_batch) {
 
 hipError_t launch_nn_delta_walk(hipStream_t st, const clrrt_sample* S, int B, const NnRec* nodes, int first, int count,
                                 const DevParams& p, const NnFrame& fr, double x0, double y0, double x1, double y1,
-                                WalkBufs& w, float* pk, int* pi, const float* ckey, const int* ncand, float* seed,
-                                bool seeded, unsigned long long* stats) {
+                                WalkBufs& w, float* pk, int* pi, float* seed, unsigned long long* stats) {
   if (count <= 0 || B <= 0) return hipSuccess;
   if (count > w.cap_nodes) return hipErrorInvalidValue;
   const int Npad = (count + WALK_TILE * WALK_SUPER - 1) / (WALK_TILE * WALK_SUPER) * (WALK_TILE * WALK_SUPER);
@@ -2057,10 +2005,6 @@ hipError_t launch_nn_delta_walk(hipStream_t st, const clrrt_sample* S, int B, co
   hipLaunchKernelGGL(k_walk_range_index, dim3(nsup), dim3(WALK_TILE * WALK_SUPER), 0, st, nodes, count,
                      (const int*)w.sids, fr.ox, fr.oy, fr.delta, w.P, w.Q, w.CE, w.ID, w.HEAD, w.trun, w.tiles, w.supers);
   LAUNCH_CHECK3();
-  if (!seeded) {
-    hipLaunchKernelGGL(k_walk_seed, dim3((B + 63) / 64), dim3(64), 0, st, B, p.sort_limit, ckey, ncand, seed);
-    LAUNCH_CHECK3();
-  }
   hipLaunchKernelGGL(k_walk_delta, dim3(B), dim3(64), 2 * sizeof(float) * (size_t)nsup, st, S, B, nodes, w.P, w.Q, w.CE,
                      w.ID, w.HEAD, w.trun, w.tiles, ntiles, w.supers, nsup, p, fr, (const float*)seed, stats, pk, pi);
   LAUNCH_CHECK3();

@@ -396,9 +396,8 @@ def test_pipelined_batch_rounds_identical():
                 dict(roll_coop=0), dict(rows_deferred=0),
                 dict(nn_walk_double=0), dict(nn_walk_budget_tiles=0, nn_walk_budget_keys=0),
                 dict(nn_walk_budget_tiles=1, nn_walk_budget_keys=1, nn_walk_chunks=5),
-                # scheduling / placement options (CU-masked rollout stream, walk streams off 2/8 of the CUs,
-                # 32 job lanes per wave, an LDS floor per walk wave) and the large-tree walk format
-                dict(cu_split=2), dict(walk_cu_reserve=2), dict(roll_lanes=32), dict(nn_walk_lds_floor=16384),
+                # a scheduling option (32 job lanes per wave) and the large-tree walk format
+                dict(roll_lanes=32),
                 dict(nn_walk_stateless=1, nn_walk_half_max=0), dict(nn_walk_waves=0), dict(nn_walk_waves=512)]
     for opts in variants:
         pl = clrrt.Planner(clrrt.default_params(collision_mode=mode), max_nodes=1 << 20, max_rows=1 << 26,
@@ -419,6 +418,39 @@ def test_pipelined_batch_rounds_identical():
     assert trees[0][2] > 20000
     for t in trees[1:]:
         assert trees[0][0] == t[0] and trees[0][1] == t[1]
+
+
+RETIRED_OPTIONS = ("cu_split", "walk_cu_reserve", "side_priority", "nn_walk_lpt", "nn_walk_lds_floor",
+                   "nn_delta_early", "nn_lane_order")
+
+
+@pytest.mark.gpu
+def test_retired_options_rejected_without_state():
+    """The scheduling options retired after their A/B measurements ("Options retired") are
+    unknown keys: clrrt_set_option returns CLRRT_EINVAL (-1) for each, and a planner that was asked for all seven
+    grows, byte for byte, the tree and rows of a fresh planner -- a rejected key leaves no state behind."""
+    mode, obs = _scene("obb200")
+    trees = []
+    for ask in (True, False):
+        pl = clrrt.Planner(clrrt.default_params(collision_mode=mode), max_nodes=1 << 12, max_rows=1 << 22,
+                           max_batch=64)
+        try:
+            if ask:
+                for key in RETIRED_OPTIONS:
+                    with pytest.raises(clrrt.ClrrtError, match=r"-> -1: unknown option or value: " + key):
+                        pl.set_option(key, 1)
+            pl.set_option("nn_walk_min", 64)
+            pl.set_option("nn_lag", 2)
+            pl.set_obstacles(obs)
+            pl.tree_init()
+            st = pl.expand(clrrt.Rng(12), n_iters=64 * 3, mode=clrrt.CLRRT_MODE_BATCH, batch=64)
+            assert st["rounds"] == 3
+            n, nr = pl.size()
+            trees.append((bytes(pl.nodes_raw()), pl.rows(0, nr).tobytes(), n))
+        finally:
+            pl.close()
+    assert trees[0][2] > 1
+    assert trees[0] == trees[1]
 
 
 @pytest.mark.gpu

@@ -72,13 +72,10 @@ def test_partial_lists_equal_brute_force(defer):
 SHAPES = [
     # batch 96: appended ranges below one tile and no multiples of 32 or 1024 (the shortest take the brute force)
     (96, 8, dict()),
-    (96, 8, dict(nn_delta_early=0)),
     (96, 8, dict(nn_delta_walk=0)),
     # batch 2048 x 5 rounds: more than one super-tile per range
     (2048, 5, dict()),
-    (2048, 5, dict(nn_delta_early=0)),
     (2048, 5, dict(nn_delta_walk=0)),
-    (2048, 5, dict(nn_delta_walk=0, nn_delta_early=0)),
     # every sample overflows its walk: the caps come from k_walk_seed_ovf
     (2048, 5, dict(nn_walk_budget_tiles=1, nn_walk_budget_keys=1)),
     (96, 8, dict(nn_walk_budget_tiles=1, nn_walk_budget_keys=1)),

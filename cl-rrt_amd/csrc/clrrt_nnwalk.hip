@@ -30,6 +30,14 @@
 //                                turns by psi >= beta (psi <= pi: the end point lies between the
 //                                arc chord bearing psi / 2 and psi), and the inside-circle case
 //                                has key >= rho * pi (checked numerically by tests/test_nnwalk_bounds.py);
+//   * tiles and super-tiles, the circle floor (walk_lb): key >= 14.9 when every record of the tile surely has the
+//     sample inside a turning circle.  With D = |s - c| > pr, ang = the angle between the tile's mean heading and
+//     s - c and A = asin(pr / D) + thh + margin, every record's unsigned bearing beta to the sample has
+//     min(beta, pi - beta) >= z = min(ang, pi - ang) - A and its distance d lies in [D - pr, D + pr].  In the node
+//     frame tx = d cos(beta), ty = d sin(beta), so t2 = tx^2 + ty (ty - 2 rho) = d^2 - 2 rho d sin(beta): for z > 0
+//     sin(beta) >= sin(z), t2 falls with sin(beta) and is convex in d, hence t2 <= max over d in {D - pr, D + pr} of
+//     d (d - 2 rho sin z).  Where that is <= -0.01 - 1e-3 every record meets walk_key_range's "surely inside" test
+//     (t2 <= -0.01), whose bound is rho pi > 14.9 (tests/test_walk_circle_bound.py);
 //   * optimize: key = costE + dubins >= costE - |p - c| + |s - c| for any point c;
 //   * feasibleNode: the direction from ref.back() to the sample must lie within pi/4 of ang_par and
 //     |sample - ref.back()| >= 2.1 ref_res.
@@ -551,13 +559,33 @@ __device__ __forceinline__ float walk_lb(const WalkTile& w, float rsx, float rsy
   const float dx = rsx - w.pcx, dy = rsy - w.pcy;
   const float D = fsqrt(dx * dx + dy * dy);
   float lb = D - w.pr;
+  bool circ = false;  // every record of the tile has the sample surely inside a turning circle
   if (D > w.pr && w.thh < 3.f) {
     const float iD = frcp(D);
-    const float al = 1.57079633f - acos_apx(w.pr * iD);
-    const float bmin = acos_apx((dx * w.thx + dy * w.thy) * iD) - al - w.thh - 3e-3f;
-    lb = fmaxf(lb, rho * bmin);
+    // every record's unsigned bearing beta to the sample lies within A of ang (A's 3e-3 covers the two
+    // acos_apx terms, 1.4e-4, and the float angle arithmetic)
+    const float A = (1.57079633f - acos_apx(w.pr * iD)) + w.thh + 3e-3f;
+    const float ang = acos_apx((dx * w.thx + dy * w.thy) * iD);
+    lb = fmaxf(lb, rho * (ang - A));
+    // Circle floor.  min(beta, pi - beta) >= z for every record; when z > 0 (0 < bmin and bmax < pi; z <= pi / 2
+    // as bmin <= bmax) sin(beta) >= sin(z) >= sm, the degree-7 Taylor sum (alternating, next term positive).  In
+    // the node frame t2 = tx^2 + ty (ty - 2 rho) = d^2 - 2 rho d sin(beta) with d in [D - pr, D + pr]: decreasing
+    // in sin(beta) and convex in d, so t2 <= U = max over both ends of d (d - 2 rho sm).  U can be negative only
+    // for d < 2 rho = 9.54, where d^2 + 2 rho d < 182, so what U leaves out is: float rounding of its products
+    // (4 ulp, 4.4e-5), of sm's terms (3e-7 through 2 rho d: 3e-5), of D and pr (1 ulp of 10 m through the gradient
+    // 2 d + 2 rho < 30: 3e-5), and the reference's own float offset and rotation (1e-6 through the same gradient:
+    // 3e-5); the frame slack is inside pr, the angle errors inside A.  Sum 1.4e-4; the margin is 1e-3.
+    // U + 1e-3 <= -0.01 is then walk_key_range's "surely inside" test for every record: key >= 14.9.
+    const float z = fminf(ang, 3.14159265f - ang) - A;
+    if (z > 0.f) {
+      const float z2 = z * z;
+      const float g = (2.f * rho) * (z + z * z2 * (-1.f / 6.f + z2 * (1.f / 120.f - z2 * (1.f / 5040.f))));
+      const float d0 = D - w.pr, d1 = D + w.pr;
+      circ = fmaxf(d0 * (d0 - g), d1 * (d1 - g)) <= -0.011f;
+    }
   }
   lb = lb - 2e-3f - 1e-5f * fabsf(lb);
+  if (circ) lb = fmaxf(lb, 14.9f);
   // optimize: costE + key >= costE + |s - p| >= (costE - |p - c|) + |s - c| for c = the tile centre
   // and for c = R (the root: near-straight branches have costE - |p - R| ~ 0, so only tiles whose
   // branches bend less than the 11th key allows survive)

@@ -23,7 +23,7 @@ def main(path):
     for r in csv.DictReader(op(path, "rt")):
         k = (int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Stream_Id"])
         n = kname(r["Kernel_Name"])
-        if r["Kernel_Name"].startswith("void clrrt::k_roll_run<false, true, true>"):
+        if r["Kernel_Name"].startswith("void clrrt::k_roll_run<false, true, true"):
             roll.append(k)
         by.setdefault(n, []).append(k)
     roll.sort()

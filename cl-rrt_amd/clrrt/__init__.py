@@ -42,6 +42,10 @@ _SIGS = {
     "clrrt_set_obstacles": (C.c_int, [C.c_void_p, P(abi.Obstacle), C.c_int32]),
     "clrrt_set_occupancy": (C.c_int, [C.c_void_p, P(abi.Occupancy), C.c_void_p]),
     "clrrt_occupancy_info": (C.c_int, [C.c_void_p, P(abi.OccupancyInfo)]),
+    "clrrt_set_occupancy_clearance": (C.c_int, [C.c_void_p, C.c_double]),
+    "clrrt_occupancy_clearance_info": (C.c_int, [C.c_void_p, P(abi.ClearanceInfo)]),
+    "clrrt_occupancy_field": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "clrrt_occupancy_clearance": (C.c_int, [C.c_void_p, P(C.c_double), C.c_int32, P(C.c_double)]),
     "clrrt_set_rank": (C.c_int, [C.c_void_p, C.c_int32]),
     "clrrt_set_shards": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, EXCHANGE_FN, C.c_void_p]),
     "clrrt_tree_init": (C.c_int, [C.c_void_p, P(C.c_double)]),
@@ -263,6 +267,32 @@ class Planner:
         o = abi.OccupancyInfo()
         self._chk(self.L.clrrt_occupancy_info(self.h, C.byref(o)), "occupancy_info")
         return {k: getattr(o, k) for k, _ in abi.OccupancyInfo._fields_}
+
+    def set_occupancy_clearance(self, clear_max):
+        """The occupancy clearance (clrrt_set_occupancy_clearance): clear_max > 0 bakes the grid's distance field now
+        and after every later set_occupancy, and under CLRRT_COLLISION_OCC a step's obstacle cost term takes
+        min(Dobs, clearance); 0 turns it off and frees the field."""
+        self._chk(self.L.clrrt_set_occupancy_clearance(self.h, float(clear_max)), "set_occupancy_clearance")
+
+    def occupancy_clearance_info(self):
+        o = abi.ClearanceInfo()
+        self._chk(self.L.clrrt_occupancy_clearance_info(self.h, C.byref(o)), "occupancy_clearance_info")
+        return {k: getattr(o, k) for k, _ in abi.ClearanceInfo._fields_}
+
+    def occupancy_field(self):
+        """The baked squared distance field, uint32 [h, w] (0xFFFFFFFF: no occupied cell)."""
+        i = self.occupancy_info()
+        out = np.empty((max(i["h"], 1), max(i["w"], 1)), dtype=np.uint32)
+        self._chk(self.L.clrrt_occupancy_field(self.h, C.c_void_p(out.ctypes.data)), "occupancy_field")
+        return out
+
+    def occupancy_clearance(self, states):
+        """The clearance of each state (rows of 10 doubles), by the device function the step loops call."""
+        st = np.ascontiguousarray(states, dtype=np.float64).reshape(-1, 10)
+        out = np.empty(len(st), dtype=np.float64)
+        self._chk(self.L.clrrt_occupancy_clearance(self.h, st.ctypes.data_as(P(C.c_double)), len(st),
+                                                   out.ctypes.data_as(P(C.c_double))), "occupancy_clearance")
+        return out
 
     def tree_init(self, root=None):
         root = np.zeros(10) if root is None else np.ascontiguousarray(root, dtype=np.float64)

@@ -61,6 +61,11 @@ class OccupancyInfo(C.Structure):  # clrrt_occupancy_info_t
                 ("map_bytes", C.c_int64), ("bake_ms", C.c_double)]
 
 
+class ClearanceInfo(C.Structure):  # clrrt_clearance_info_t
+    _fields_ = [("clear_max", C.c_double), ("on", C.c_int32), ("baked", C.c_int32), ("field_bytes", C.c_int64),
+                ("bake_ms", C.c_double)]
+
+
 class Node(C.Structure):
     _fields_ = [
         ("state", C.c_double * 10), ("ref_front", C.c_double * 2), ("ref_back", C.c_double * 2),
@@ -129,6 +134,7 @@ def _check_sizes():
     assert C.sizeof(RolloutResult) == 136, C.sizeof(RolloutResult)
     assert C.sizeof(ExchangeIO) == 128, C.sizeof(ExchangeIO)
     assert C.sizeof(Occupancy) == 40 and C.sizeof(OccupancyInfo) == 48
+    assert C.sizeof(ClearanceInfo) == 32
 
 
 _check_sizes()

@@ -116,6 +116,13 @@ struct clrrt_ctx {
   int64_t occ_count = 0;
   hipEvent_t occ_ev[2] = {nullptr, nullptr};
   float occ_bake_ms = 0.f;
+  // the occupancy clearance (clrrt_set_occupancy_clearance): its cap (0: off), the field's buffer (field dwords | row
+  // distances | row mask; occ.field points into it while a field is baked) and the field bake's events
+  double clr_max = 0.0;
+  void* clr_buf = nullptr;
+  size_t clr_bytes = 0;
+  hipEvent_t clr_ev[2] = {nullptr, nullptr};
+  float clr_bake_ms = 0.f;
   // round buffers (capacity cap.max_batch samples)
   // The list sets: sets[] owns the buffers (sets 0 and 1 from clrrt_create, set 2 and the lag-2 members of all three
   // from lag_alloc; free_all frees sets[] alone), ls[] names them by role: ls[0] this round's set, ls[1] the set the
@@ -666,7 +673,7 @@ static void free_all(clrrt_ctx* c) {
   if (c->side) hipStreamSynchronize(c->side);  // side-stream work (prefetched search) uses a list set
   void* ptrs[] = {c->tree, c->nn, c->arena, c->obs, c->pk, c->pi, c->sort_scratch, c->res_spec, c->regnodes,
                   c->res_gb, c->gbnodes, c->so, c->first_conflict,
-                  c->out_nodes, c->jobs, c->slots, c->rep_buf, c->totals, c->work_ctr, c->grid_buf, c->occ_buf,
+                  c->out_nodes, c->jobs, c->slots, c->rep_buf, c->totals, c->work_ctr, c->grid_buf, c->occ_buf, c->clr_buf,
                   c->nn_seed, c->d_bbox, c->roll_q, c->roll_best, c->roll_perm, c->roll_pflag,
                   c->goal_recs, c->bp_path, c->path_nodes, c->path_rows, c->ri_int, c->ri_off, c->ri_cost,
                   c->ri_terms, c->nnw.keys, c->nnw.keys2, c->nnw.vals, c->nnw.vals2, c->nnw.tmp, c->nnw.P, c->nnw.Q,
@@ -687,6 +694,8 @@ static void free_all(clrrt_ctx* c) {
   for (void* p : dptrs)
     if (p) hipFree(p);
   for (auto e : c->occ_ev)
+    if (e) hipEventDestroy(e);
+  for (auto e : c->clr_ev)
     if (e) hipEventDestroy(e);
   if (c->side2) hipStreamSynchronize(c->side2);
   if (c->side2) hipStreamDestroy(c->side2);
@@ -1034,6 +1043,36 @@ int clrrt_set_obstacles(clrrt_ctx* c, const clrrt_obstacle* o, int32_t m) {
   return build_grid(c, b);
 }
 
+// The distance field of the grid in c->occ (set, clearance on), baked on the context's stream, which the caller has
+// drained of launches that read the old field; on success c->occ carries it.
+static int bake_field(clrrt_ctx* c) {
+  OccGrid& g = c->occ;
+  g.field = nullptr;
+  g.clear_max = 0.0;
+  c->clr_bake_ms = 0.f;
+  const size_t ncell = (size_t)g.w * g.h;
+  const size_t field_b = (sizeof(uint32_t) * ncell + 255) / 256 * 256, rowd_b = (sizeof(uint16_t) * ncell + 255) / 256 * 256;
+  const size_t need = field_b + rowd_b + 64 * sizeof(uint32_t);
+  if (need > c->clr_bytes) {
+    if (c->clr_buf) HIPC(c, hipFree(c->clr_buf));
+    c->clr_buf = nullptr;
+    c->clr_bytes = 0;
+    HIPC(c, hipMalloc(&c->clr_buf, need));
+    c->clr_bytes = need;
+  }
+  for (auto& e : c->clr_ev)
+    if (!e) HIPC(c, hipEventCreate(&e));
+  char* b = (char*)c->clr_buf;
+  HIPC(c, hipEventRecord(c->clr_ev[0], c->stream));
+  HIPC(c, launch_occ_field(c->stream, g, (uint16_t*)(b + field_b), (uint32_t*)(b + field_b + rowd_b), (uint32_t*)b));
+  HIPC(c, hipEventRecord(c->clr_ev[1], c->stream));
+  HIPC(c, hipStreamSynchronize(c->stream));
+  HIPC(c, hipEventElapsedTime(&c->clr_bake_ms, c->clr_ev[0], c->clr_ev[1]));
+  g.field = (const uint32_t*)b;
+  g.clear_max = c->clr_max;
+  return CLRRT_OK;
+}
+
 int clrrt_set_occupancy(clrrt_ctx* c, const clrrt_occupancy* o, const uint8_t* cells) {
   if (!c) return CLRRT_EINVAL;
   HIPC(c, hipSetDevice(c->device));
@@ -1107,6 +1146,68 @@ int clrrt_set_occupancy(clrrt_ctx* c, const clrrt_occupancy* o, const uint8_t* c
   HIPC(c, hipEventElapsedTime(&c->occ_bake_ms, c->occ_ev[0], c->occ_ev[1]));
   c->occ = g;
   c->occ_count = count;
+  if (c->clr_max > 0.0) return bake_field(c);
+  return CLRRT_OK;
+}
+
+int clrrt_set_occupancy_clearance(clrrt_ctx* c, double clear_max) {
+  if (!c) return CLRRT_EINVAL;
+  if (!(clear_max >= 0.0 && std::isfinite(clear_max)))
+    return fail(c, CLRRT_EINVAL, "set_occupancy_clearance: clear_max = " + std::to_string(clear_max) +
+                                     " is not 0 (off) or finite and > 0");
+  HIPC(c, hipSetDevice(c->device));
+  const int frc = flush_replays(c);  // pending replays are costed as the scene they were committed with
+  if (frc != CLRRT_OK) return frc;
+  HIPC(c, hipStreamSynchronize(c->stream));  // (no launch still reads the old field)
+  c->clr_max = clear_max;
+  if (clear_max == 0.0) {
+    c->occ.field = nullptr;
+    c->occ.clear_max = 0.0;
+    c->clr_bake_ms = 0.f;
+    if (c->clr_buf) HIPC(c, hipFree(c->clr_buf));
+    c->clr_buf = nullptr;
+    c->clr_bytes = 0;
+    return CLRRT_OK;
+  }
+  if (c->occ.w > 0) return bake_field(c);
+  return CLRRT_OK;
+}
+
+int clrrt_occupancy_clearance_info(clrrt_ctx* c, clrrt_clearance_info_t* out) {
+  if (!c || !out) return CLRRT_EINVAL;
+  memset(out, 0, sizeof(*out));
+  out->clear_max = c->clr_max;
+  out->on = c->clr_max > 0.0;
+  out->baked = c->occ.field != nullptr;
+  out->field_bytes = out->baked ? (int64_t)sizeof(uint32_t) * c->occ.w * c->occ.h : 0;
+  out->bake_ms = c->clr_bake_ms;
+  return CLRRT_OK;
+}
+
+int clrrt_occupancy_field(clrrt_ctx* c, uint32_t* out) {
+  if (!c || !out) return CLRRT_EINVAL;
+  if (!c->occ.field) return fail(c, CLRRT_ESTATE, "occupancy_field: no field is baked (clrrt_set_occupancy_clearance with a grid set)");
+  HIPC(c, hipSetDevice(c->device));
+  HIPC(c, hipMemcpyAsync(out, c->occ.field, sizeof(uint32_t) * (size_t)c->occ.w * c->occ.h, hipMemcpyDeviceToHost, c->stream));
+  HIPC(c, hipStreamSynchronize(c->stream));
+  return CLRRT_OK;
+}
+
+int clrrt_occupancy_clearance(clrrt_ctx* c, const double* states, int32_t n, double* out) {
+  if (!c || n < 0 || (n > 0 && (!states || !out))) return CLRRT_EINVAL;
+  if (!c->occ.field) return fail(c, CLRRT_ESTATE, "occupancy_clearance: no field is baked (clrrt_set_occupancy_clearance with a grid set)");
+  HIPC(c, hipSetDevice(c->device));
+  if (n == 0) return CLRRT_OK;
+  double *din = nullptr, *dout = nullptr;
+  hipError_t e = hipMalloc((void**)&din, sizeof(double) * 10 * (size_t)n);
+  if (e == hipSuccess) e = hipMalloc((void**)&dout, sizeof(double) * (size_t)n);
+  if (e == hipSuccess) e = hipMemcpyAsync(din, states, sizeof(double) * 10 * (size_t)n, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = launch_occ_clearance(c->stream, c->occ, din, n, dout);
+  if (e == hipSuccess) e = hipMemcpyAsync(out, dout, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  hipFree(din);
+  hipFree(dout);
+  if (e != hipSuccess) return fail(c, CLRRT_EHIP, std::string("occupancy_clearance: ") + hipGetErrorString(e));
   return CLRRT_OK;
 }
 

@@ -94,10 +94,14 @@ struct ObsGrid {
 // The static occupancy grid of CLRRT_COLLISION_OCC as the kernels see it (baked by clrrt_set_occupancy, see
 // clrrt_occ.hpp): the bit-packed occupancy map (cell (i, j): bit i & 31 of occ[j ws + (i >> 5)]) and the reach map
 // (rw x rh cells of rk x rk occupancy cells each, rm cells of margin around the grid, rows of rws words).  w == 0:
-// no grid (the mode-1 instantiations run).  in_lds / lds_off: set per launch (occ_place).
+// no grid (the mode-1 instantiations run).  in_lds / lds_off: set per launch (occ_place).  field: the squared
+// distance field of clrrt_set_occupancy_clearance (w x h dwords, global memory; null: clearance off or not baked),
+// clear_max its cap.
 struct OccGrid {
   const uint32_t* occ;
   const uint32_t* reach;
+  const uint32_t* field;
+  double clear_max;
   double x0, y0, res, inflate;
   double rx0, ry0, rres;
   int w, h, ws;
@@ -407,6 +411,11 @@ hipError_t launch_obs_distance(hipStream_t st, const DevParams& p, const BakedOb
 // clrrt_set_occupancy's bake: the cell bytes into g.occ, then g.reach from it; Rc = the reach radius in cells
 // (clrrt_occ.hpp), *count += occupied cells.
 hipError_t launch_occ_bake(hipStream_t st, const uint8_t* cells, const OccGrid& g, double Rc, unsigned int* count);
+// clrrt_set_occupancy_clearance's bake (clrrt_occ.hpp): the squared distance field of g.occ into field (w h dwords),
+// through the row distances rowd (w h halfwords) and the non-empty-row mask rowmask (64 words, zeroed here).
+hipError_t launch_occ_field(hipStream_t st, const OccGrid& g, uint16_t* rowd, uint32_t* rowmask, uint32_t* field);
+// Clearance of n states (10 doubles each) against g.field, by the step loops' device function.
+hipError_t launch_occ_clearance(hipStream_t st, const OccGrid& g, const double* states, int n, double* out);
 // Bytes of the two maps, and whether the persistent rollout launch of these arguments holds them in LDS.
 size_t occ_map_bytes(const OccGrid& g);
 bool roll_occ_in_lds(const RollArgs& a);

@@ -991,13 +991,15 @@ __device__ __forceinline__ double roll_step_pre(Roll& r, const DevParams& p, dou
   return d2;
 }
 
-__device__ __forceinline__ int roll_step_post(Roll& r, const DevParams& p, double Dobs, double d2) {
+// Dcost: the distance the obstacle cost term takes -- Dobs, or under an occupancy clearance occ_cost_gap's value, which
+// reaches the cost line without passing through the collision test.
+__device__ __forceinline__ int roll_step_post(Roll& r, const DevParams& p, double Dobs, double d2, double Dcost) {
   if (Dobs == 0) return CLRRT_ROLL_COLLISION;  // simulation.cpp:83-86
   // costs (simulation.cpp:89-95)
   r.costE += r.x4 * p.dt;
   double kappa = r.t3 / p.L;
   double term = p.W0 * r.x4 * p.dt + p.W1 * fabs(kappa);
-  if (p.use_exp) term = term + p.W2 * glibc::exp(-p.W3 * Dobs);  // glibc's exp, restated
+  if (p.use_exp) term = term + p.W2 * glibc::exp(-p.W3 * Dcost);  // glibc's exp, restated
   r.costS += term;
   if (p.bend) r.costS += p.W4 * dist_to_lane(r.x0, r.x1, p.lane_shift0, p.Cxy1, p.Cxy2);
   // lateral acceleration limit (simulation.cpp:98-104)
@@ -1032,8 +1034,11 @@ __device__ __forceinline__ int roll_step(Roll& r, const DevParams& p, const ObsV
   double Dobs;
   if constexpr (OCC) Dobs = obs_distance_occ<NEED_GAP>(r, p, ov, oc, w.box);
   else Dobs = obs_distance<NEED_GAP>(r, p, ov, w.box);
+  double Dcost = Dobs;
+  if constexpr (OCC && NEED_GAP)
+    Dcost = occ_cost_gap(oc, Dobs, r.x0 + 1.424 * r.c2, r.x1 + 1.424 * r.s2, r.x2, r.c2, r.s2);
   if (pc) pc->mark(4);
-  return roll_step_post(r, p, Dobs, d2);
+  return roll_step_post(r, p, Dobs, d2, Dcost);
 }
 
 // Wave-cooperative checkObsDistance without the gap value (k_roll_run; OBB collision with the static
@@ -2009,8 +2014,11 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CLRRT_
     } else {
       Dobs = obs_distance<NEED_GAP>(r, P, ov, w.box);
     }
+    double Dcost = Dobs;
+    if constexpr (OCC && NEED_GAP)
+      Dcost = occ_cost_gap(oc, Dobs, r.x0 + 1.424 * r.c2, r.x1 + 1.424 * r.s2, r.x2, r.c2, r.s2);
     if (pc) pc->mark(4);
-    int o = roll_step_post(r, P, Dobs, d2);
+    int o = roll_step_post(r, P, Dobs, d2, Dcost);
 #ifdef CLRRT_ROLL_PROFILE
     job_steps++;
     chain_steps = max(chain_steps, job_steps);
@@ -2695,9 +2703,12 @@ __global__ void __launch_bounds__(256) k_tree_reinit(ReinitArgs a) {
       if constexpr (OCC) Dobs = obs_distance_occ<true>(r, p, ov, oc, tests);
       else Dobs = obs_distance<true>(r, p, ov, tests);
       if (Dobs == 0) s_coll = 1;
+      double Dcost = Dobs;
+      if constexpr (OCC)
+        if (p.use_exp) Dcost = occ_cost_gap(oc, Dobs, r.x0 + 1.424 * r.c2, r.x1 + 1.424 * r.s2, r.x2, r.c2, r.s2);
       const double kappa = glibc::tan(x[3]) / p.L;
       double term = p.W0 * x[4] * p.dt + p.W1 * fabs(kappa);
-      if (p.use_exp) term = term + p.W2 * glibc::exp(-p.W3 * Dobs);  // glibc's exp, restated
+      if (p.use_exp) term = term + p.W2 * glibc::exp(-p.W3 * Dcost);  // glibc's exp, restated
       double* t = a.terms + (a.koff[k] + i) * 2;
       t[0] = term;
       t[1] = p.bend ? p.W4 * dist_to_lane(x[0], x[1], p.lane_shift0, p.Cxy1, p.Cxy2) : 0.0;
@@ -2985,6 +2996,18 @@ __global__ void k_obs_distance(DevParams p, const BakedObs* __restrict__ obs, co
   } else {
     out[i] = obs_distance<true>(r, p, ov, tests);
   }
+}
+
+// clrrt_occupancy_clearance: occ_clearance (the step loops' device function) for n states of 10 doubles, with the
+// heading's cosine and sine as the step holds them (glibc::sincos).
+__global__ void k_occ_clearance(OccGrid og, const double* __restrict__ st, int n, double* __restrict__ out) {
+  glibc::stage_tables();
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double* x = st + 10 * (int64_t)i;
+  double sn, cs;
+  glibc::sincos(x[2], sn, cs);
+  out[i] = occ_clearance(og, x[0] + 1.424 * cs, x[1] + 1.424 * sn, x[2], cs, sn);
 }
 
 // Test hook (clrrt_selftest_collision): the rollout kernels' collision decision for explicit states, one state
@@ -3652,6 +3675,25 @@ hipError_t launch_occ_bake(hipStream_t st, const uint8_t* cells, const OccGrid& 
   LAUNCH_CHECK();
   hipLaunchKernelGGL(k_occ_reach, dim3((unsigned)((nr + 255) / 256)), dim3(256), 0, st, g.occ, g.w, g.h, g.ws, g.rk,
                      g.rm, Rc, g.rw, g.rh, g.rws, const_cast<uint32_t*>(g.reach));
+  LAUNCH_CHECK();
+  return hipSuccess;
+}
+
+hipError_t launch_occ_field(hipStream_t st, const OccGrid& g, uint16_t* rowd, uint32_t* rowmask, uint32_t* field) {
+  const int64_t np = (int64_t)g.h * g.ws * 32, nc = (int64_t)g.w * g.h;
+  hipError_t e = hipMemsetAsync(rowmask, 0, 64 * sizeof(uint32_t), st);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_occ_field_rows, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st, g.occ, g.w, g.h, g.ws, rowd,
+                     rowmask);
+  LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_occ_field_cols, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, st, rowd, rowmask, g.w, g.h,
+                     field);
+  LAUNCH_CHECK();
+  return hipSuccess;
+}
+
+hipError_t launch_occ_clearance(hipStream_t st, const OccGrid& g, const double* states, int n, double* out) {
+  hipLaunchKernelGGL(k_occ_clearance, dim3((n + 255) / 256), dim3(256), 0, st, g, states, n, out);
   LAUNCH_CHECK();
   return hipSuccess;
 }

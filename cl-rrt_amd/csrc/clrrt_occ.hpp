@@ -85,6 +85,101 @@ __global__ void __launch_bounds__(256) k_occ_reach(const uint32_t* __restrict__ 
   }
 }
 
+// ------------------------------------------------------------------------------------------------ distance field
+// The squared Euclidean distance field of clrrt_set_occupancy_clearance: field[j w + i] = min over occupied cells
+// (i', j') of (i - i')^2 + (j - j')^2, exact in uint32 (at most 2 * 2047^2), OCC_FIELD_NONE without an occupied cell.
+// Separable: the row pass writes each cell's distance to the nearest occupied cell of its own row, the column pass
+// takes min over rows j' of (j - j')^2 + rowd[j'][i]^2.
+#define OCC_FIELD_NONE 0xFFFFFFFFu
+#define OCC_ROWD_NONE 0xFFFFu
+
+// Row pass, one lane per cell of a row padded to 64 cells as in k_occ_pack.  A row has at most 64 words, so lane q of
+// every wave holds word q of the wave's row and the ballot of the non-zero ones; a cell's nearest occupied cell on
+// either side is in its own word (clz / ctz of the masked word) or in the nearest non-zero word on that side (clz /
+// ctz of the ballot, the word fetched by a shuffle).  The padding bits are 0.  Rows with an occupied cell are marked
+// in rowmask (bit j & 31 of word j >> 5).
+__global__ void __launch_bounds__(256) k_occ_field_rows(const uint32_t* __restrict__ occ, int w, int h, int ws,
+                                                        uint16_t* __restrict__ rowd, uint32_t* __restrict__ rowmask) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int rowbits = ws * 32;
+  const int64_t j = idx / rowbits;
+  const int i = (int)(idx % rowbits);
+  if (j >= h) return;  // (wave-uniform: a wave lies in one row)
+  const int lane = threadIdx.x & 63;
+  const uint32_t word = lane < ws ? occ[j * ws + lane] : 0u;
+  const unsigned long long nz = __ballot(word != 0u);
+  if (i == 0 && nz) atomicOr(&rowmask[j >> 5], 1u << (j & 31));
+  const int qi = i >> 5, b = i & 31;
+  const uint32_t own = (uint32_t)__shfl((int)word, qi, 64);
+  const uint32_t ml = own & (~0u >> (31 - b));  // occupied cells of the own word at or left of i
+  const uint32_t mr = own & (~0u << b);         // at or right of i
+  const unsigned long long nzl = nz & ((1ull << qi) - 1ull);
+  const unsigned long long nzr = qi >= 63 ? 0ull : nz & (~0ull << (qi + 1));
+  const int ql = nzl ? 63 - __clzll((long long)nzl) : 0;
+  const int qr = nzr ? __ffsll((long long)nzr) - 1 : 0;
+  const uint32_t wl = (uint32_t)__shfl((int)word, ql, 64);
+  const uint32_t wr = (uint32_t)__shfl((int)word, qr, 64);
+  int dl = (int)OCC_ROWD_NONE, dr = (int)OCC_ROWD_NONE;
+  if (ml) dl = b - (31 - __clz((int)ml));
+  else if (nzl) dl = i - (ql * 32 + 31 - __clz((int)wl));
+  if (mr) dr = (__ffs((int)mr) - 1) - b;
+  else if (nzr) dr = qr * 32 + (__ffs((int)wr) - 1) - i;
+  if (i < w) rowd[j * w + i] = (uint16_t)min(dl, dr);
+}
+
+// The nearest non-empty row at or below / at or above j (-1: none); nw = words of the mask.
+__device__ __forceinline__ int occ_row_prev(const uint32_t* __restrict__ m, int j) {
+  int q = j >> 5;
+  uint32_t x = m[q] & (~0u >> (31 - (j & 31)));
+  while (!x) {
+    if (--q < 0) return -1;
+    x = m[q];
+  }
+  return q * 32 + 31 - __clz((int)x);
+}
+__device__ __forceinline__ int occ_row_next(const uint32_t* __restrict__ m, int j, int nw) {
+  int q = j >> 5;
+  uint32_t x = m[q] & (~0u << (j & 31));
+  while (!x) {
+    if (++q >= nw) return -1;
+    x = m[q];
+  }
+  return q * 32 + __ffs((int)x) - 1;
+}
+
+// Column pass, one lane per cell, adjacent lanes on adjacent columns (the loads of a row coalesce): a windowed
+// minimum over the non-empty rows, outward from the cell's own row in both directions, that stops where (j - j')^2
+// alone reaches the best so far -- no row farther out can lower it.  The row skip makes a nearly empty map (the
+// window's worst case) cost a few rows per cell.
+__global__ void __launch_bounds__(256) k_occ_field_cols(const uint16_t* __restrict__ rowd,
+                                                        const uint32_t* __restrict__ rowmask, int w, int h,
+                                                        uint32_t* __restrict__ field) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (int64_t)w * h) return;
+  const int j = (int)(idx / w), i = (int)(idx % w);
+  const int nw = (h + 31) >> 5;
+  uint32_t best = OCC_FIELD_NONE;
+  const uint32_t g0 = rowd[idx];
+  if (g0 != OCC_ROWD_NONE) best = g0 * g0;
+  for (int jj = j - 1; jj >= 0; jj--) {
+    jj = occ_row_prev(rowmask, jj);
+    if (jj < 0) break;
+    const uint32_t d = (uint32_t)(j - jj);
+    if (d * d >= best) break;
+    const uint32_t g = rowd[(int64_t)jj * w + i];  // (a marked row has a distance in every cell)
+    best = min(best, d * d + g * g);
+  }
+  for (int jj = j + 1; jj < h; jj++) {
+    jj = occ_row_next(rowmask, jj, nw);
+    if (jj < 0) break;
+    const uint32_t d = (uint32_t)(jj - j);
+    if (d * d >= best) break;
+    const uint32_t g = rowd[(int64_t)jj * w + i];
+    best = min(best, d * d + g * g);
+  }
+  field[idx] = best;
+}
+
 // ------------------------------------------------------------------------------------------------ step test
 // The maps a kernel reads: the grid record (a kernel argument: scalar loads) and the two bitmaps, in LDS
 // (occ_stage) or global memory; scans counts the lane's steps that took the exact scan.
@@ -147,6 +242,40 @@ __device__ __forceinline__ bool occ_hit(OccView& ov, double vpx, double vpy, dou
     }
   }
   return false;
+}
+
+// One step's clearance from the distance field g.field (non-null; include/clrrt.h, clrrt_set_occupancy_clearance):
+// three circles of radius OCC_CLR_RC along the heading cover the vehicle box; each centre inside the grid reads its
+// cell's squared distance (one dword from global memory), the smallest one gives the distance -- sqrt and the
+// product with res are monotonic, so the minimum is taken over the integers -- and a centre outside the grid, a
+// non-finite state or a map without an occupied cell leaves +inf, which the cap turns into clear_max.  All in double.
+#define OCC_CLR_RC 1.2857 /* circle radius: half width 1 and a third of the half length, 0.808, under one hypotenuse */
+#define OCC_CLR_S 1.616   /* spacing of the circle centres along the box axis */
+__device__ __forceinline__ double occ_clearance(const OccGrid& g, double vpx, double vpy, double th, double cs,
+                                                double sn) {
+  uint32_t m = OCC_FIELD_NONE;
+  if (isfinite(vpx) && isfinite(vpy) && isfinite(th)) {
+#pragma unroll
+    for (int k = -1; k <= 1; k++) {
+      const double px = k ? vpx + (k * OCC_CLR_S) * cs : vpx, py = k ? vpy + (k * OCC_CLR_S) * sn : vpy;
+      const double fx = (px - g.x0) / g.res, fy = (py - g.y0) / g.res;
+      if (fx >= 0.0 && fx < (double)g.w && fy >= 0.0 && fy < (double)g.h) m = min(m, g.field[(int)fy * g.w + (int)fx]);
+    }
+  }
+  const double d = m == OCC_FIELD_NONE ? (double)INFINITY : g.res * sqrt((double)m);
+  double c = d - (OCC_CLR_RC + g.inflate);
+  c = fmin(c, g.clear_max);
+  return fmax(c, 0.0);
+}
+
+// The value the obstacle cost term takes for a step that does not collide (Dobs != 0): min(Dobs, clearance) where
+// the field is baked and on, Dobs otherwise.  It does not pass through the collision test (the circles overhang the
+// box, so the clearance can be 0 on a state that does not hit).
+__device__ __forceinline__ double occ_cost_gap(const OccView& ov, double Dobs, double vpx, double vpy, double th,
+                                               double cs, double sn) {
+  if (ov.g->field == nullptr || Dobs == 0) return Dobs;
+  const double c = occ_clearance(*ov.g, vpx, vpy, th, cs, sn);
+  return c < Dobs ? c : Dobs;
 }
 
 }  // namespace clrrt

@@ -258,6 +258,42 @@ typedef struct {
   double bake_ms;          /* device time of the last bake (upload + kernels) */
 } clrrt_occupancy_info_t;
 int clrrt_occupancy_info(clrrt_ctx* ctx, clrrt_occupancy_info_t* out);
+/* Occupancy clearance: the grid's distance in the obstacle cost term (engine extension; off by default, and with it
+ * off every result and every launch is what it is without these functions).
+ *   Field.  f[j][i] = min over occupied cells (i', j') of (i - i')^2 + (j - j')^2, an exact integer held as uint32;
+ * 0xFFFFFFFF: no cell is occupied.  It is baked on the device and lives in global memory (4 w h bytes).
+ *   Clearance of a state x.  With cs, sn the cosine and sine of x[2] as the step holds them and
+ * vp = (x[0] + 1.424 cs, x[1] + 1.424 sn), three circles of radius RC = 1.2857 with centres p_k = vp + s_k (cs, sn),
+ * s_k in {-1.616, 0.0, +1.616}, cover the 4.848 x 2 vehicle box.  f_x = (p_k.x - x0) / res, f_y = (p_k.y - y0) / res;
+ * the centre is inside when 0 <= f_x < w and 0 <= f_y < h (NaN fails all four); inside,
+ * d_k = res sqrt((double) f[(int) f_y][(int) f_x]), otherwise, or with no occupied cell, d_k = +inf.
+ * c = min_k d_k - (RC + inflate), then c = min(c, clear_max), then c = max(c, 0.0): all in double, in this order,
+ * without FMA contraction.  A non-finite heading or position gives clear_max.
+ *   Where it enters.  In collision mode 2, with a grid set, clearance on and Wcost[2] * exp(-Wcost[3] * D) able to be
+ * non-zero, a step that does not collide takes D = min(Dobs, c) in that term, Dobs being checkObsDistance's value:
+ * in the rollouts of clrrt_expand, clrrt_rollout_batch and clrrt_simulate and in the re-init cost of
+ * clrrt_tree_init_from_path.  Nothing else reads it: a step collides exactly when it does with clearance off (c can
+ * be 0 on a state that does not hit -- the circles overhang the box), clrrt_obstacle_distance is unchanged, and since
+ * tree growth does not read costS the tree grown is the same in everything but costS and what
+ * clrrt_extract_best_path picks from it.
+ *   clear_max > 0 and finite turns it on: the field of the current grid is baked now and again after every later
+ * clrrt_set_occupancy.  0 turns it off and frees the field.  Anything else is CLRRT_EINVAL, naming the value.  It
+ * first lands the deferred rows of committed nodes, as clrrt_set_occupancy does.  Legal in any collision mode, read
+ * only in mode 2.  Under sharding every rank sets the same value. */
+int clrrt_set_occupancy_clearance(clrrt_ctx* ctx, double clear_max);
+typedef struct {
+  double clear_max;     /* 0: off */
+  int32_t on;           /* clear_max > 0 */
+  int32_t baked;        /* a field of the current grid is on the device */
+  int64_t field_bytes;  /* 4 w h when baked, else 0 */
+  double bake_ms;       /* device time of the last field bake (its kernels only) */
+} clrrt_clearance_info_t;
+int clrrt_occupancy_clearance_info(clrrt_ctx* ctx, clrrt_clearance_info_t* out);
+/* The w h field values, row j at out + j w.  CLRRT_ESTATE without a baked field. */
+int clrrt_occupancy_field(clrrt_ctx* ctx, uint32_t* out);
+/* c of n states (10 doubles each), evaluated on the device by the device function the step loops call.  CLRRT_ESTATE
+ * without a baked field. */
+int clrrt_occupancy_clearance(clrrt_ctx* ctx, const double* states, int32_t n, double* out);
 int clrrt_set_rank(clrrt_ctx* ctx, int32_t rank);
 
 /* ---- tree ---- */

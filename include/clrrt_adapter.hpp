@@ -183,6 +183,12 @@ class Engine {
     const bool clear = occ.w == 0 || !cells;
     check(ctx_, clrrt_set_occupancy(ctx_, clear ? nullptr : &occ, clear ? nullptr : cells), "clrrt_set_occupancy");
   }
+  /* The occupancy clearance (clrrt_set_occupancy_clearance): clear_max > 0 puts the grid's distance into the obstacle
+   * cost term of mode 2, capped at clear_max; 0 turns it off. */
+  void setOccupancyClearance(double clear_max) {
+    drop_cache();
+    check(ctx_, clrrt_set_occupancy_clearance(ctx_, clear_max), "clrrt_set_occupancy_clearance");
+  }
 
   /* The device tree := RRT.tree (e.g. after MyRRT::addInitialNode or initializeTree). */
   template <class RRTT>
@@ -804,6 +810,13 @@ class MotionPlanner {
     grid_ = grid;
     grid_dirty_ = true;
   }
+  /* The occupancy clearance (clrrt_set_occupancy_clearance): clear_max > 0 puts the grid's distance into the obstacle
+   * cost term, capped at clear_max; 0 turns it off.  Held across queries and applied at the next planMotion with the
+   * grid of updateOccupancy.  Under sharding every rank is given the same value. */
+  void setOccupancyClearance(double clear_max) {
+    clear_max_ = clear_max;
+    clear_dirty_ = true;
+  }
 
   /* One query.  Returns false when no path was found ("No solution found", :56-58): the committed path
    * is then empty and the next query restarts from the car state. */
@@ -827,6 +840,10 @@ class MotionPlanner {
       check(ctx_, clrrt_set_occupancy(ctx_, none ? nullptr : &grid_.dims, none ? nullptr : grid_.cells.data()),
             "clrrt_set_occupancy");
       grid_dirty_ = false;
+    }
+    if (clear_dirty_) {
+      check(ctx_, clrrt_set_occupancy_clearance(ctx_, clear_max_), "clrrt_set_occupancy_clearance");
+      clear_dirty_ = false;
     }
     check(ctx_, clrrt_path_transform(ctx_, CLRRT_WORLD_TO_CAR, world), "clrrt_path_transform");          // :22
     if (!cfg_.commit_path) check(ctx_, clrrt_path_commit(ctx_, nullptr, 0, nullptr), "clrrt_path_commit");  // :28-30
@@ -917,6 +934,8 @@ class MotionPlanner {
   std::vector<clrrt_obstacle> det_;
   OccupancyGrid grid_;
   bool grid_dirty_ = false;
+  double clear_max_ = 0.0;
+  bool clear_dirty_ = false;
   int32_t (*completer_)(void*, clrrt_ctx*, int64_t*) = nullptr;
   void* completer_user_ = nullptr;
 };

@@ -11,7 +11,13 @@ Per run: rollout-kernel ms per launch (clrrt_kernel_time family 1), the share of
 grid's exact scan (raw work counter 3 over work counter 0), nodes grown.  Then the bake time of 512 x 512 and
 2048 x 2048 grids (2 % random fill; clrrt_occupancy_info).  Writes a text summary (default profiles/occ_grid.txt).
 
-  python tools/occ_bench.py [--runs 3] [--modes 1,2] [--out profiles/occ_grid.txt] [--label text]
+  mode 2g  mode 2 with Wcost[2] = 2 (the gap-value instantiation of the rollout kernels), clearance off
+  mode 2gc the same with the occupancy clearance on (clrrt_set_occupancy_clearance, clear_max 3): the difference to
+           2g is the distance-field lookups
+With 2gc among the modes, the field bake time (clrrt_occupancy_clearance_info) of 512 x 512 and 2048 x 2048 grids at
+1 % random fill and with a single occupied cell follows.
+
+  python tools/occ_bench.py [--runs 3] [--modes 1,2,2g,2gc] [--out profiles/occ_grid.txt] [--label text]
 """
 import argparse
 import os
@@ -29,14 +35,17 @@ B, ROUNDS, DEFER = 16384, 8, 128
 GRID = dict(x0=0.0, y0=-26.0, res=0.2, w=330, h=260)
 
 
-def grow(mode, obs, cells):
-    pl = clrrt.Planner(clrrt.default_params(collision_mode=mode), max_nodes=1 << 20, max_rows=1 << 26, max_batch=B,
-                       max_obstacles=max(1, len(obs)))
+def grow(mode, obs, cells, w2=0.0, clear_max=0.0):
+    params = clrrt.default_params(collision_mode=mode)
+    params.Wcost[2] = w2
+    pl = clrrt.Planner(params, max_nodes=1 << 20, max_rows=1 << 26, max_batch=B, max_obstacles=max(1, len(obs)))
     try:
         pl.set_option("defer_steps", DEFER)
         pl.set_obstacles(obs)
         if cells is not None:
             pl.set_occupancy(GRID["x0"], GRID["y0"], GRID["res"], cells)
+        if clear_max:
+            pl.set_occupancy_clearance(clear_max)
         pl.enable_timing(True)
         pl.tree_init()
         st = pl.expand(clrrt.Rng(1), n_iters=B * ROUNDS, mode=clrrt.CLRRT_MODE_BATCH, batch=B)
@@ -63,6 +72,25 @@ def bake(n, runs):
         pl.close()
 
 
+def field_bake(n, single, runs):
+    if single:
+        cells = np.zeros((n, n), np.uint8)
+        cells[n // 3, n // 5] = 1
+    else:
+        cells = (np.random.default_rng(n).random((n, n)) < 0.01).astype(np.uint8)
+    pl = clrrt.Planner(clrrt.default_params(collision_mode=abi.CLRRT_COLLISION_OCC), max_nodes=1 << 10,
+                       max_rows=1 << 14, max_batch=64)
+    try:
+        pl.set_occupancy_clearance(3.0)
+        out = []
+        for _ in range(runs + 1):  # the first call allocates
+            pl.set_occupancy(-0.05 * n, -0.05 * n, 0.1, cells)
+            out.append((pl.occupancy_clearance_info()["bake_ms"], pl.occupancy_info()["bake_ms"]))
+        return out[1:]
+    finally:
+        pl.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--runs", type=int, default=3)
@@ -73,16 +101,20 @@ def main():
     obs = scenes.urban_scene(200)
     lines = [f"occ_bench {args.label}: cfg3 scene (200 static boxes), {B} samples x {ROUNDS} rounds, defer_steps {DEFER}; "
              f"library {os.path.relpath(clrrt.LIB_PATH, ROOT)}"]
-    for mode in (int(m) for m in args.modes.split(",") if m):
+    for name in (m for m in args.modes.split(",") if m):
+        mode = int(name[0])
         if mode == 2 and not hasattr(abi, "CLRRT_COLLISION_OCC"):
             continue
+        if name == "2gc" and not hasattr(clrrt.Planner, "set_occupancy_clearance"):
+            continue
         cells = scenes.rasterize(obs, **GRID) if mode == 2 else None
-        res = [grow(mode, obs if mode == 1 else obs[:0], cells) for _ in range(args.runs)]
+        res = [grow(mode, obs if mode == 1 else obs[:0], cells, 2.0 if "g" in name else 0.0,
+                    3.0 if name == "2gc" else 0.0) for _ in range(args.runs)]
         ms = [r["ms_per_launch"] for r in res]
-        lines.append(f"mode {mode}: rollout kernel ms per launch {' '.join('%.3f' % v for v in ms)} (spread "
+        lines.append(f"mode {name}: rollout kernel ms per launch {' '.join('%.3f' % v for v in ms)} (spread "
                      f"{(max(ms) - min(ms)) / min(ms) * 100:.1f} %), launches {res[0]['launches']}, nodes "
                      f"{res[0]['nodes']}, steps {res[0]['steps']}")
-        if mode == 2:
+        if name == "2":
             r = res[0]
             lines.append(f"mode 2: grid {GRID['w']} x {GRID['h']} at res {GRID['res']}, {r['info']['occupied']} occupied "
                          f"cells, maps {r['info']['map_bytes']} B in "
@@ -93,6 +125,13 @@ def main():
             b = bake(n, args.runs)
             lines.append(f"bake {n} x {n} (2 % fill, {b[0]['occupied']} occupied, reach map {b[0]['reach_w']} x "
                          f"{b[0]['reach_h']}): {' '.join('%.3f' % v['bake_ms'] for v in b)} ms (upload + kernels)")
+    if "2gc" in args.modes.split(",") and hasattr(clrrt.Planner, "set_occupancy_clearance"):
+        for n in (512, 2048):
+            for single in (False, True):
+                b = field_bake(n, single, args.runs)
+                lines.append(f"field bake {n} x {n} ({'one occupied cell' if single else '1 % fill'}): "
+                             f"{' '.join('%.3f' % v[0] for v in b)} ms (kernels), beside the map bake's "
+                             f"{' '.join('%.3f' % v[1] for v in b)} ms (upload + kernels)")
     text = "\n".join(lines) + "\n"
     print(text, end="")
     if args.out:

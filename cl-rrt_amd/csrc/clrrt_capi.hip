@@ -30,6 +30,7 @@
 
 #include "../../include/clrrt.h"
 #include "clrrt_dev.hpp"
+#include "clrrt_devmem_hip.hpp"
 #include "clrrt_internal.hpp"
 
 static const int kWalkMaxOver = 2048, kWalkMaxChunks = 64;  // walk overflow records, split waves per record
@@ -38,11 +39,6 @@ using namespace clrrt;
 
 #define CAND_K 10
 #define NN_K 11
-
-struct DevBuf {
-  void* p = nullptr;
-  size_t bytes = 0;
-};
 
 // One round's samples and candidate lists.  The context keeps three sets and names them by role (clrrt_ctx::ls).
 struct ListSet {
@@ -96,6 +92,9 @@ struct clrrt_ctx {
   DevParams dp;
   clrrt_capacity cap;
   std::string err;
+  // Every device and pinned buffer below (and in the WalkBufs, ListSet, def and sh groups) is allocated through `mem`
+  // (renew / renew_host) and freed by it: free_all's release_all, after the streams have drained.
+  clrrt::DevMem<HipMem> mem;
   // tree
   clrrt_node* tree = nullptr;
   NnRec* nn = nullptr;
@@ -124,8 +123,8 @@ struct clrrt_ctx {
   hipEvent_t clr_ev[2] = {nullptr, nullptr};
   float clr_bake_ms = 0.f;
   // round buffers (capacity cap.max_batch samples)
-  // The list sets: sets[] owns the buffers (sets 0 and 1 from clrrt_create, set 2 and the lag-2 members of all three
-  // from lag_alloc; free_all frees sets[] alone), ls[] names them by role: ls[0] this round's set, ls[1] the set the
+  // The list sets: sets[] holds the buffers (sets 0 and 1 from clrrt_create, set 2 and the lag-2 members of all three
+  // from lag_alloc), ls[] names them by role: ls[0] this round's set, ls[1] the set the
   // side stream searches for the next round (lag 2: round r+1's, being merged), ls[2] lag 2's round r+2's, being
   // searched.  ls[] is a permutation of &sets[0..2] at every instant, so any exit leaves a context safe to free and
   // to reuse.
@@ -445,13 +444,12 @@ static int fail(clrrt_ctx* c, int code, const std::string& msg) {
     if (e_ != hipSuccess)                                                                      \
       return fail((c), CLRRT_EHIP, std::string(#call) + ": " + hipGetErrorString(e_));        \
   } while (0)
-
-template <typename T>
-static hipError_t dalloc(T** p, size_t count) {
-  *p = nullptr;
-  if (count == 0) count = 1;
-  return hipMalloc((void**)p, count * sizeof(T));
-}
+// as HIPC, for the entry points whose failures read "<entry>: <error>"
+#define HIPP(c, prefix, call)                                                                  \
+  do {                                                                                         \
+    hipError_t e_ = (call);                                                                    \
+    if (e_ != hipSuccess) return fail((c), CLRRT_EHIP, std::string(prefix) + hipGetErrorString(e_)); \
+  } while (0)
 
 static hipEvent_t ev_get(clrrt_ctx* c) {
   if (!c->ev_pool.empty()) {
@@ -659,82 +657,34 @@ int clrrt_draw_samples(const clrrt_params* p, clrrt_rng* rng, int32_t n, clrrt_s
 const char* clrrt_last_error(const clrrt_ctx* c) { return c ? c->err.c_str() : "null context"; }
 
 // The six buffers of a list set for batches of B samples.
-static hipError_t alloc_lists(ListSet& s, int64_t B) {
-  hipError_t e = dalloc(&s.d_samples, B);
-  if (e == hipSuccess) e = hipHostMalloc((void**)&s.h_samples, sizeof(clrrt_sample) * B, hipHostMallocDefault);
-  if (e == hipSuccess) e = dalloc(&s.cand, B * CAND_K);
-  if (e == hipSuccess) e = dalloc(&s.ckey, B * CAND_K);
-  if (e == hipSuccess) e = dalloc(&s.ncand, B);
-  if (e == hipSuccess) e = dalloc(&s.ctie, B);
-  return e;
+static int alloc_lists(clrrt_ctx* c, ListSet& s, int64_t B) {
+  HIPC(c, c->mem.renew(&s.d_samples, B));
+  HIPC(c, c->mem.renew_host(&s.h_samples, B));
+  HIPC(c, c->mem.renew(&s.cand, B * CAND_K));
+  HIPC(c, c->mem.renew(&s.ckey, B * CAND_K));
+  HIPC(c, c->mem.renew(&s.ncand, B));
+  HIPC(c, c->mem.renew(&s.ctie, B));
+  return CLRRT_OK;
 }
 
+// Drain the streams that exist, then the memory, then the events and the streams themselves.
 static void free_all(clrrt_ctx* c) {
-  if (c->side) hipStreamSynchronize(c->side);  // side-stream work (prefetched search) uses a list set
-  void* ptrs[] = {c->tree, c->nn, c->arena, c->obs, c->pk, c->pi, c->sort_scratch, c->res_spec, c->regnodes,
-                  c->res_gb, c->gbnodes, c->so, c->first_conflict,
-                  c->out_nodes, c->jobs, c->slots, c->rep_buf, c->totals, c->work_ctr, c->grid_buf, c->occ_buf, c->clr_buf,
-                  c->nn_seed, c->d_bbox, c->roll_q, c->roll_best, c->roll_perm, c->roll_pflag,
-                  c->goal_recs, c->bp_path, c->path_nodes, c->path_rows, c->ri_int, c->ri_off, c->ri_cost,
-                  c->ri_terms, c->nnw.keys, c->nnw.keys2, c->nnw.vals, c->nnw.vals2, c->nnw.tmp, c->nnw.P, c->nnw.Q,
-                  c->nnw.CE, c->nnw.ID, c->nnw.tiles, c->nnw.supers, c->nnw.sorder, c->nnw.HEAD, c->nnw.ovf_n, c->nnw.ovf, c->nnw.pk, c->nnw.pi, c->nnw_alt.keys, c->nnw_alt.keys2, c->nnw_alt.vals, c->nnw_alt.vals2, c->nnw_alt.tmp, c->nnw_alt.P, c->nnw_alt.Q, c->nnw_alt.CE, c->nnw_alt.ID, c->nnw_alt.tiles, c->nnw_alt.supers, c->nnw_alt.sorder, c->nnw_alt.HEAD, c->nnw_alt.ovf_n, c->nnw_alt.ovf, c->nnw_alt.pk, c->nnw_alt.pi, c->nnw.skeys, c->nnw.sids, c->nnw_alt.skeys, c->nnw_alt.sids, c->cmp.packed, c->cmp.scanned,
-                  c->cmp.tmp, c->nnw3.keys, c->nnw3.keys2, c->nnw3.vals, c->nnw3.vals2, c->nnw3.tmp, c->nnw3.P,
-                  c->nnw3.Q, c->nnw3.CE, c->nnw3.ID, c->nnw3.tiles, c->nnw3.supers, c->nnw3.sorder, c->nnw3.HEAD,
-                  c->nnw3.ovf_n, c->nnw3.ovf, c->nnw3.pk, c->nnw3.pi, c->nnw3.skeys, c->nnw3.sids,
-                  c->nnw.trun, c->nnw_alt.trun, c->nnw3.trun, c->nnw.wctr, c->nnw_alt.wctr, c->nnw3.wctr};
-  for (void* p : ptrs)
-    if (p) hipFree(p);
-  void* sptrs[] = {c->sh.xbuf, c->sh.xkey, c->sh.xtmp, c->sh.d_goal, c->fix_n, c->fix_ids, c->fix_jobs, c->fix_res, c->fix_adj,
-                   c->fix_xrec, c->fix_xi, c->fix_xcand, c->fix_xkey, c->fix_xn};
-  for (void* p : sptrs)
-    if (p) hipFree(p);
-  void* dptrs[] = {c->def.res, c->def.res_gb, c->def.cand, c->def.ncand, c->def.samp, c->def.best, c->def.dlist[0],
-                   c->def.dlist[1], c->def.gv, c->def.pend, c->def.sel_tmp, c->def.d_cnt, c->def.carry[0],
-                   c->def.carry[1]};
-  for (void* p : dptrs)
-    if (p) hipFree(p);
+  for (hipStream_t s : {c->side, c->side2, c->mst, c->stream})
+    if (s) hipStreamSynchronize(s);
+  c->mem.release_all();
   for (auto e : c->occ_ev)
     if (e) hipEventDestroy(e);
   for (auto e : c->clr_ev)
     if (e) hipEventDestroy(e);
-  if (c->side2) hipStreamSynchronize(c->side2);
-  if (c->side2) hipStreamDestroy(c->side2);
-  if (c->mst) hipStreamSynchronize(c->mst);
-  if (c->mst) hipStreamDestroy(c->mst);
-  for (ListSet& s : c->sets) {  // the storage, whatever roles ls[] gives the sets
-    for (void* p : {(void*)s.d_samples, (void*)s.cand, (void*)s.ckey, (void*)s.ncand, (void*)s.ctie, (void*)s.wseed})
-      if (p) hipFree(p);
-    if (s.h_samples) hipHostFree(s.h_samples);
+  for (ListSet& s : c->sets)
     for (hipEvent_t e : {s.ev, s.evw, s.evm})
       if (e) hipEventDestroy(e);
-  }
-  if (c->nn_order) hipFree(c->nn_order);
-  {
-    WalkBufs& d = c->nnw_d;
-    void* wd[] = {d.keys, d.vals, d.tmp, d.P, d.Q, d.CE, d.ID, d.HEAD, d.trun, d.tiles, d.supers, d.skeys, d.sids,
-                  c->vpk, c->vpi, c->vseed};
-    for (void* p : wd)
-      if (p) hipFree(p);
-  }
-  {
-    WalkBufs& r = c->nnw_r;
-    void* wr[] = {r.keys, r.keys2, r.vals, r.vals2, r.tmp, r.P, r.Q, r.CE, r.ID, r.tiles, r.supers, r.sorder, r.HEAD,
-                  r.ovf_n, r.ovf, r.pk, r.pi, r.skeys, r.sids, r.trun, r.wctr, c->pm_ids, c->pm_keys, c->pm_counts,
-                  c->d_bad};
-    for (void* p : wr)
-      if (p) hipFree(p);
-  }
-  if (c->side) hipStreamSynchronize(c->side);
-  if (c->ev_tree) hipEventDestroy(c->ev_tree);
-  if (c->ev_walk) hipEventDestroy(c->ev_walk);
-  if (c->ev_commit) hipEventDestroy(c->ev_commit);
-  if (c->side) hipStreamDestroy(c->side);
-  if (c->h_totals) hipHostFree(c->h_totals);
-  if (c->h_int) hipHostFree(c->h_int);
-  if (c->h_bbox) hipHostFree(c->h_bbox);
-  if (c->dbg_host) hipHostFree(c->dbg_host);
+  for (hipEvent_t e : {c->ev_tree, c->ev_walk, c->ev_commit})
+    if (e) hipEventDestroy(e);
   for (auto& pe : c->ev_pending) { hipEventDestroy(pe.second.first); hipEventDestroy(pe.second.second); }
   for (auto e : c->ev_pool) hipEventDestroy(e);
+  for (hipStream_t s : {c->side2, c->mst, c->side})
+    if (s) hipStreamDestroy(s);
   if (c->own_stream && c->stream) hipStreamDestroy(c->stream);
 }
 
@@ -767,49 +717,50 @@ int clrrt_create(const clrrt_params* p, const clrrt_capacity* cap, int device, c
   chk(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
   c->own_stream = true;
   const int64_t B = c->cap.max_batch;
-  chk(dalloc(&c->tree, c->cap.max_nodes));
-  chk(dalloc(&c->nn, c->cap.max_nodes));
-  chk(dalloc(&c->arena, (size_t)c->cap.max_rows * 10));
-  chk(dalloc(&c->obs, std::max<int64_t>(1, c->cap.max_obstacles)));
-  for (int q = 0; q < 2; q++) chk(alloc_lists(c->sets[q], B));
+  chk(c->mem.renew(&c->tree, c->cap.max_nodes));
+  chk(c->mem.renew(&c->nn, c->cap.max_nodes));
+  chk(c->mem.renew(&c->arena, (size_t)c->cap.max_rows * 10));
+  chk(c->mem.renew(&c->obs, std::max<int64_t>(1, c->cap.max_obstacles)));
+  for (int q = 0; q < 2; q++)
+    if (rc == CLRRT_OK) rc = alloc_lists(c, c->sets[q], B);
   c->partial_cap = std::max<int64_t>(B * 16, 4096) * NN_K;
-  chk(dalloc(&c->pk, c->partial_cap));
-  chk(dalloc(&c->pi, c->partial_cap));
+  chk(c->mem.renew(&c->pk, c->partial_cap));
+  chk(c->mem.renew(&c->pi, c->partial_cap));
   chk(hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking));
   chk(hipEventCreateWithFlags(&c->ev_tree, hipEventDisableTiming));
   chk(hipEventCreateWithFlags(&c->ev_walk, hipEventDisableTiming));
   chk(hipEventCreateWithFlags(&c->ev_commit, hipEventDisableTiming));
-  chk(dalloc(&c->res_spec, B * CAND_K));
-  chk(dalloc(&c->regnodes, B));
-  chk(dalloc(&c->res_gb, B * CAND_K));
+  chk(c->mem.renew(&c->res_spec, B * CAND_K));
+  chk(c->mem.renew(&c->regnodes, B));
+  chk(c->mem.renew(&c->res_gb, B * CAND_K));
   c->slot_rows = 0;  // slots allocated on first use (ensure_slots)
-  chk(hipMalloc(&c->rep_buf, replay_bytes() * (size_t)2 * B));
-  chk(dalloc(&c->gbnodes, B));
-  chk(dalloc(&c->so, B));
-  chk(dalloc(&c->first_conflict, 1));
-  chk(dalloc(&c->out_nodes, 2 * B));
-  chk(dalloc(&c->jobs, 2 * B));
-  chk(dalloc(&c->totals, 8));
-  chk(dalloc(&c->cmp.packed, B));
-  chk(dalloc(&c->cmp.scanned, B));
+  chk(c->mem.renew_bytes(&c->rep_buf, replay_bytes() * (size_t)2 * B));
+  chk(c->mem.renew(&c->gbnodes, B));
+  chk(c->mem.renew(&c->so, B));
+  chk(c->mem.renew(&c->first_conflict, 1));
+  chk(c->mem.renew(&c->out_nodes, 2 * B));
+  chk(c->mem.renew(&c->jobs, 2 * B));
+  chk(c->mem.renew(&c->totals, 8));
+  chk(c->mem.renew(&c->cmp.packed, B));
+  chk(c->mem.renew(&c->cmp.scanned, B));
   c->cmp.tmp_bytes = compact_scan_bytes((int)B);
-  chk(hipMalloc(&c->cmp.tmp, std::max<size_t>(c->cmp.tmp_bytes, 256)));
-  chk(dalloc(&c->nn_seed, B));
-  chk(dalloc(&c->roll_q, 1));
-  chk(dalloc(&c->roll_best, B));
-  chk(dalloc(&c->roll_perm, (int64_t)B * CAND_K));
-  chk(dalloc(&c->roll_pflag, (int64_t)roll_order_ints((int)(B * CAND_K))));
+  chk(c->mem.renew_bytes(&c->cmp.tmp, std::max<size_t>(c->cmp.tmp_bytes, 256)));
+  chk(c->mem.renew(&c->nn_seed, B));
+  chk(c->mem.renew(&c->roll_q, 1));
+  chk(c->mem.renew(&c->roll_best, B));
+  chk(c->mem.renew(&c->roll_perm, (int64_t)B * CAND_K));
+  chk(c->mem.renew(&c->roll_pflag, (int64_t)roll_order_ints((int)(B * CAND_K))));
   {
     int ncu = 0;
     if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && ncu > 0)
       c->n_cu = ncu;
   }
-  chk(dalloc(&c->d_bbox, 4));
-  chk(hipHostMalloc((void**)&c->h_bbox, sizeof(double) * 4, hipHostMallocDefault));
-  chk(dalloc(&c->work_ctr, 64));
+  chk(c->mem.renew(&c->d_bbox, 4));
+  chk(c->mem.renew_host(&c->h_bbox, 4));
+  chk(c->mem.renew(&c->work_ctr, 64));
   if (rc == CLRRT_OK) chk(hipMemset(c->work_ctr, 0, 64 * sizeof(unsigned long long)));
-  chk(hipHostMalloc((void**)&c->h_totals, sizeof(int64_t) * 8, hipHostMallocDefault));
-  chk(hipHostMalloc((void**)&c->h_int, sizeof(int) * 4, hipHostMallocDefault));
+  chk(c->mem.renew_host(&c->h_totals, 8));
+  chk(c->mem.renew_host(&c->h_int, 4));
   if (rc != CLRRT_OK) {
     fprintf(stderr, "clrrt_create: %s\n", c->err.c_str());
     free_all(c);
@@ -823,7 +774,6 @@ int clrrt_create(const clrrt_params* p, const clrrt_capacity* cap, int device, c
 void clrrt_destroy(clrrt_ctx* c) {
   if (!c) return;
   hipSetDevice(c->device);
-  if (c->stream) hipStreamSynchronize(c->stream);
   free_all(c);
   delete c;
 }
@@ -858,10 +808,8 @@ int clrrt_set_params(clrrt_ctx* c, const clrrt_params* p) {
   if (c->slots && d.n_steps_max + 1 > c->slot_rows) {  // a smaller sim_dt needs longer rollout slots
     HIPC(c, hipSetDevice(c->device));
     HIPC(c, hipStreamSynchronize(c->stream));
-    HIPC(c, hipFree(c->slots));
-    c->slots = nullptr;
     c->slot_rows = 0;
-    HIPC(c, dalloc(&c->slots, (size_t)2 * (d.n_steps_max + 1) * 10 * c->cap.max_batch * CAND_K));
+    HIPC(c, c->mem.renew(&c->slots, (size_t)2 * (d.n_steps_max + 1) * 10 * c->cap.max_batch * CAND_K));
     c->slot_rows = d.n_steps_max + 1;
   }
   c->params = *p;
@@ -956,10 +904,8 @@ static int build_grid(clrrt_ctx* c, const std::vector<BakedObs>& b) {
   if (gw == 0) { start.clear(); items.clear(); }
   size_t need = 4 * start.size() + 2 * (items.size() + mov.size()) + 16;
   if (need > c->grid_bytes) {
-    if (c->grid_buf) HIPC(c, hipFree(c->grid_buf));
-    c->grid_buf = nullptr;
     c->grid_bytes = 0;
-    HIPC(c, hipMalloc(&c->grid_buf, need));
+    HIPC(c, c->mem.renew_bytes(&c->grid_buf, need));
     c->grid_bytes = need;
   }
   std::vector<uint8_t> host(need, 0);
@@ -1054,10 +1000,8 @@ static int bake_field(clrrt_ctx* c) {
   const size_t field_b = (sizeof(uint32_t) * ncell + 255) / 256 * 256, rowd_b = (sizeof(uint16_t) * ncell + 255) / 256 * 256;
   const size_t need = field_b + rowd_b + 64 * sizeof(uint32_t);
   if (need > c->clr_bytes) {
-    if (c->clr_buf) HIPC(c, hipFree(c->clr_buf));
-    c->clr_buf = nullptr;
     c->clr_bytes = 0;
-    HIPC(c, hipMalloc(&c->clr_buf, need));
+    HIPC(c, c->mem.renew_bytes(&c->clr_buf, need));
     c->clr_bytes = need;
   }
   for (auto& e : c->clr_ev)
@@ -1121,11 +1065,9 @@ int clrrt_set_occupancy(clrrt_ctx* c, const clrrt_occupancy* o, const uint8_t* c
   if (frc != CLRRT_OK) return frc;
   HIPC(c, hipStreamSynchronize(c->stream));  // (no launch still reads the old maps)
   if (need > c->occ_bytes) {
-    if (c->occ_buf) HIPC(c, hipFree(c->occ_buf));
-    c->occ_buf = nullptr;
     c->occ_bytes = 0;
     c->occ = OccGrid{};
-    HIPC(c, hipMalloc(&c->occ_buf, need));
+    HIPC(c, c->mem.renew_bytes(&c->occ_buf, need));
     c->occ_bytes = need;
   }
   for (auto& e : c->occ_ev)
@@ -1164,9 +1106,8 @@ int clrrt_set_occupancy_clearance(clrrt_ctx* c, double clear_max) {
     c->occ.field = nullptr;
     c->occ.clear_max = 0.0;
     c->clr_bake_ms = 0.f;
-    if (c->clr_buf) HIPC(c, hipFree(c->clr_buf));
-    c->clr_buf = nullptr;
     c->clr_bytes = 0;
+    HIPC(c, c->mem.release(&c->clr_buf));
     return CLRRT_OK;
   }
   if (c->occ.w > 0) return bake_field(c);
@@ -1198,16 +1139,14 @@ int clrrt_occupancy_clearance(clrrt_ctx* c, const double* states, int32_t n, dou
   if (!c->occ.field) return fail(c, CLRRT_ESTATE, "occupancy_clearance: no field is baked (clrrt_set_occupancy_clearance with a grid set)");
   HIPC(c, hipSetDevice(c->device));
   if (n == 0) return CLRRT_OK;
-  double *din = nullptr, *dout = nullptr;
-  hipError_t e = hipMalloc((void**)&din, sizeof(double) * 10 * (size_t)n);
-  if (e == hipSuccess) e = hipMalloc((void**)&dout, sizeof(double) * (size_t)n);
-  if (e == hipSuccess) e = hipMemcpyAsync(din, states, sizeof(double) * 10 * (size_t)n, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = launch_occ_clearance(c->stream, c->occ, din, n, dout);
-  if (e == hipSuccess) e = hipMemcpyAsync(out, dout, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  hipFree(din);
-  hipFree(dout);
-  if (e != hipSuccess) return fail(c, CLRRT_EHIP, std::string("occupancy_clearance: ") + hipGetErrorString(e));
+  const char* const pre = "occupancy_clearance: ";
+  Scratch<double> din, dout;
+  HIPP(c, pre, din.alloc(10 * (size_t)n));
+  HIPP(c, pre, dout.alloc(n));
+  HIPP(c, pre, hipMemcpyAsync(din, states, sizeof(double) * 10 * (size_t)n, hipMemcpyHostToDevice, c->stream));
+  HIPP(c, pre, launch_occ_clearance(c->stream, c->occ, din, n, dout));
+  HIPP(c, pre, hipMemcpyAsync(out, dout, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  HIPP(c, pre, hipStreamSynchronize(c->stream));
   return CLRRT_OK;
 }
 
@@ -1233,13 +1172,11 @@ int clrrt_tree_init(clrrt_ctx* c, const double root_state[10]) {
   pf_reset(c);
   c->rep_n = 0;  // replays pending for the old tree's rows: the tree is replaced
   HIPC(c, hipSetDevice(c->device));
-  double* d_state = nullptr;
-  HIPC(c, hipMalloc((void**)&d_state, 10 * sizeof(double)));
-  hipError_t e = hipMemcpyAsync(d_state, root_state, 10 * sizeof(double), hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = launch_init_root(c->stream, d_state, c->tree, c->nn, c->arena);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  hipFree(d_state);
-  if (e != hipSuccess) return fail(c, CLRRT_EHIP, std::string("tree_init: ") + hipGetErrorString(e));
+  Scratch<double> d_state;
+  HIPC(c, d_state.alloc(10));  // (HIPC, not HIPP: this failure never carried the prefix)
+  HIPP(c, "tree_init: ", hipMemcpyAsync(d_state, root_state, 10 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPP(c, "tree_init: ", launch_init_root(c->stream, d_state, c->tree, c->nn, c->arena));
+  HIPP(c, "tree_init: ", hipStreamSynchronize(c->stream));
   c->n_nodes = 1;
   c->n_rows = 1;
   bbox_reset(c);
@@ -1255,13 +1192,11 @@ int clrrt_tree_load(clrrt_ctx* c, const clrrt_node* nodes, int64_t n) {
   if (n > c->cap.max_nodes) return fail(c, CLRRT_ECAPACITY, "tree_load: too many nodes");
   HIPC(c, hipSetDevice(c->device));
   if (n > 0) {
-    clrrt_node* tmp = nullptr;
-    HIPC(c, hipMalloc((void**)&tmp, sizeof(clrrt_node) * n));
-    hipError_t e = hipMemcpyAsync(tmp, nodes, sizeof(clrrt_node) * n, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = launch_append(c->stream, tmp, (int)n, 0, c->tree, c->nn);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    hipFree(tmp);
-    if (e != hipSuccess) return fail(c, CLRRT_EHIP, std::string("tree_load: ") + hipGetErrorString(e));
+    Scratch<clrrt_node> tmp;
+    HIPC(c, tmp.alloc(n));  // (HIPC, not HIPP: this failure never carried the prefix)
+    HIPP(c, "tree_load: ", hipMemcpyAsync(tmp, nodes, sizeof(clrrt_node) * n, hipMemcpyHostToDevice, c->stream));
+    HIPP(c, "tree_load: ", launch_append(c->stream, tmp, (int)n, 0, c->tree, c->nn));
+    HIPP(c, "tree_load: ", hipStreamSynchronize(c->stream));
   }
   c->n_nodes = n;
   c->n_rows = 0;
@@ -1346,9 +1281,9 @@ int clrrt_extract_best_path(clrrt_ctx* c, int32_t* path, int32_t cap, int32_t* n
   if (n_goal) *n_goal = 0;
   const int64_t n = c->n_nodes;
   if (n == 0) return CLRRT_OK;
-  if (!c->goal_recs) {
-    HIPC(c, hipMalloc(&c->goal_recs, sizeof(GoalRec) * c->cap.max_nodes));
-    HIPC(c, hipMalloc(&c->bp_path, sizeof(int) * (c->cap.max_nodes + 2)));
+  if (!c->bp_path) {  // allocated last: marks the pair complete
+    HIPC(c, c->mem.renew(&c->goal_recs, c->cap.max_nodes));
+    HIPC(c, c->mem.renew(&c->bp_path, c->cap.max_nodes + 2));
   }
   int* d_cnt = c->bp_path + c->cap.max_nodes;
   HIPC(c, launch_goal_gather(c->stream, c->tree, n, c->goal_recs, d_cnt));
@@ -1391,24 +1326,18 @@ int clrrt_extract_best_path(clrrt_ctx* c, int32_t* path, int32_t cap, int32_t* n
 static int path_reserve(clrrt_ctx* c, int n, int64_t nrows) {
   if (n > c->path_cap) {
     const int cap = std::max(n, 2 * c->path_cap);
-    for (void* p : {(void*)c->path_nodes, (void*)c->ri_int, (void*)c->ri_off, (void*)c->ri_cost})
-      if (p) hipFree(p);
-    c->path_nodes = nullptr; c->ri_int = nullptr; c->ri_off = nullptr; c->ri_cost = nullptr;
     c->path_cap = 0;
-    HIPC(c, hipMalloc((void**)&c->path_nodes, sizeof(clrrt_node) * cap));
-    HIPC(c, hipMalloc((void**)&c->ri_int, sizeof(int) * (3 * (size_t)cap)));
-    HIPC(c, hipMalloc((void**)&c->ri_off, sizeof(int64_t) * ((size_t)cap + 3)));
-    HIPC(c, hipMalloc((void**)&c->ri_cost, sizeof(float) * cap));
+    HIPC(c, c->mem.renew(&c->path_nodes, cap));
+    HIPC(c, c->mem.renew(&c->ri_int, 3 * (size_t)cap));
+    HIPC(c, c->mem.renew(&c->ri_off, (size_t)cap + 3));
+    HIPC(c, c->mem.renew(&c->ri_cost, cap));
     c->path_cap = cap;
   }
   if (nrows > c->path_rows_cap) {
     const int64_t cap = std::max<int64_t>(nrows, 2 * c->path_rows_cap);
-    if (c->path_rows) hipFree(c->path_rows);
-    if (c->ri_terms) hipFree(c->ri_terms);
-    c->path_rows = nullptr; c->ri_terms = nullptr;
     c->path_rows_cap = 0;
-    HIPC(c, hipMalloc((void**)&c->path_rows, sizeof(double) * 10 * cap));
-    HIPC(c, hipMalloc((void**)&c->ri_terms, sizeof(double) * 2 * cap));
+    HIPC(c, c->mem.renew(&c->path_rows, 10 * (size_t)cap));
+    HIPC(c, c->mem.renew(&c->ri_terms, 2 * (size_t)cap));
     c->path_rows_cap = cap;
   }
   return CLRRT_OK;
@@ -1786,11 +1715,9 @@ static RollArgs roll_args(clrrt_ctx* c, int njobs) {
 static int ensure_sort_scratch(clrrt_ctx* c, int64_t entries) {
   if (entries <= c->sort_cap) return CLRRT_OK;
   HIPC(c, hipStreamSynchronize(c->stream));
-  if (c->sort_scratch) HIPC(c, hipFree(c->sort_scratch));
-  c->sort_scratch = nullptr;
   c->sort_cap = 0;
   int64_t want = std::max<int64_t>(entries, 1 << 20);
-  HIPC(c, hipMalloc((void**)&c->sort_scratch, sizeof(KeyId) * want));
+  HIPC(c, c->mem.renew(&c->sort_scratch, want));
   c->sort_cap = want;
   return CLRRT_OK;
 }
@@ -1800,33 +1727,33 @@ static int alloc_walk(clrrt_ctx* c, WalkBufs& w) {
   if (w.P) return CLRRT_OK;
   const int64_t M = std::max<int64_t>(c->cap.max_nodes, c->cap.max_batch);
   const int64_t Mp = c->cap.max_nodes + 1024;
-  HIPC(c, dalloc(&w.sorder, c->cap.max_batch));
-  HIPC(c, dalloc(&w.keys, 2 * M));
-  HIPC(c, dalloc(&w.keys2, 2 * M));
-  HIPC(c, dalloc(&w.vals, std::max<int64_t>(M, Mp)));  // also the run markers of the padded records
-  HIPC(c, dalloc(&w.vals2, M));
+  HIPC(c, c->mem.renew(&w.sorder, c->cap.max_batch));
+  HIPC(c, c->mem.renew(&w.keys, 2 * M));
+  HIPC(c, c->mem.renew(&w.keys2, 2 * M));
+  HIPC(c, c->mem.renew(&w.vals, std::max<int64_t>(M, Mp)));  // also the run markers of the padded records
+  HIPC(c, c->mem.renew(&w.vals2, M));
   w.tmp_bytes = walk_sort_bytes((int)M);
-  HIPC(c, hipMalloc(&w.tmp, std::max<size_t>(w.tmp_bytes, 256)));
-  HIPC(c, dalloc(&w.Q, Mp));
-  HIPC(c, dalloc(&w.CE, Mp));
-  HIPC(c, dalloc(&w.ID, Mp));
-  HIPC(c, dalloc(&w.HEAD, Mp));
-  HIPC(c, dalloc(&w.trun, walk_tile_count(c->cap.max_nodes) + 1));
+  HIPC(c, c->mem.renew_bytes(&w.tmp, std::max<size_t>(w.tmp_bytes, 256)));
+  HIPC(c, c->mem.renew(&w.Q, Mp));
+  HIPC(c, c->mem.renew(&w.CE, Mp));
+  HIPC(c, c->mem.renew(&w.ID, Mp));
+  HIPC(c, c->mem.renew(&w.HEAD, Mp));
+  HIPC(c, c->mem.renew(&w.trun, walk_tile_count(c->cap.max_nodes) + 1));
   // one record per tile / super-tile of the padded index (launch_nn_walk_build)
-  HIPC(c, dalloc(&w.tiles, walk_tile_count(c->cap.max_nodes) + 1));
-  HIPC(c, dalloc(&w.supers, walk_super_count(c->cap.max_nodes) + 1));
-  HIPC(c, dalloc(&w.ovf_n, 1));
-  HIPC(c, dalloc(&w.ovf, kWalkMaxOver));
-  HIPC(c, dalloc(&w.wctr, 8 + 2 + 64));  // + the root roster (count, X, 64 ids), freed with it
+  HIPC(c, c->mem.renew(&w.tiles, walk_tile_count(c->cap.max_nodes) + 1));
+  HIPC(c, c->mem.renew(&w.supers, walk_super_count(c->cap.max_nodes) + 1));
+  HIPC(c, c->mem.renew(&w.ovf_n, 1));
+  HIPC(c, c->mem.renew(&w.ovf, kWalkMaxOver));
+  HIPC(c, c->mem.renew(&w.wctr, 8 + 2 + 64));  // + the root roster (count, X, 64 ids)
   w.roster = w.wctr + 8;
-  HIPC(c, dalloc(&w.pk, (int64_t)kWalkMaxOver * kWalkMaxChunks * 11));
-  HIPC(c, dalloc(&w.pi, (int64_t)kWalkMaxOver * kWalkMaxChunks * 11));
-  HIPC(c, dalloc(&w.skeys, Mp));
-  HIPC(c, dalloc(&w.sids, Mp));
+  HIPC(c, c->mem.renew(&w.pk, (int64_t)kWalkMaxOver * kWalkMaxChunks * 11));
+  HIPC(c, c->mem.renew(&w.pi, (int64_t)kWalkMaxOver * kWalkMaxChunks * 11));
+  HIPC(c, c->mem.renew(&w.skeys, Mp));
+  HIPC(c, c->mem.renew(&w.sids, Mp));
   w.sorted_n = -1;
   w.cap_nodes = c->cap.max_nodes;
   w.cap_batch = (int)c->cap.max_batch;
-  HIPC(c, dalloc(&w.P, Mp));  // last: marks the set complete
+  HIPC(c, c->mem.renew(&w.P, Mp));  // last: marks the set complete
   return CLRRT_OK;
 }
 
@@ -2031,16 +1958,16 @@ static int exact_fixups(clrrt_ctx* c, int n, int* L) {
   const int64_t B = c->cap.max_batch;
   const int K = CAND_K;
   if (!c->fix_n) {
-    HIPC(c, dalloc(&c->fix_n, B));
-    HIPC(c, dalloc(&c->fix_ids, B * FIX_MAX));
-    HIPC(c, dalloc(&c->fix_adj, B * 5));
-    HIPC(c, dalloc(&c->fix_jobs, B * K));
-    HIPC(c, dalloc(&c->fix_res, B * K));
-    HIPC(c, dalloc(&c->fix_xrec, 2 * B));
-    HIPC(c, dalloc(&c->fix_xi, 2 * B));
-    HIPC(c, dalloc(&c->fix_xcand, B * K));
-    HIPC(c, dalloc(&c->fix_xkey, B * K));
-    HIPC(c, dalloc(&c->fix_xn, 2 * B));
+    HIPC(c, c->mem.renew(&c->fix_n, B));
+    HIPC(c, c->mem.renew(&c->fix_ids, B * FIX_MAX));
+    HIPC(c, c->mem.renew(&c->fix_adj, B * 5));
+    HIPC(c, c->mem.renew(&c->fix_jobs, B * K));
+    HIPC(c, c->mem.renew(&c->fix_res, B * K));
+    HIPC(c, c->mem.renew(&c->fix_xrec, 2 * B));
+    HIPC(c, c->mem.renew(&c->fix_xi, 2 * B));
+    HIPC(c, c->mem.renew(&c->fix_xcand, B * K));
+    HIPC(c, c->mem.renew(&c->fix_xkey, B * K));
+    HIPC(c, c->mem.renew(&c->fix_xn, 2 * B));
   }
   {
     KTimer kt(c, 2);
@@ -2312,7 +2239,7 @@ static int eval_samples(clrrt_ctx* c, int n, bool exact, int* L_out, bool have_l
     }
     unsigned long long*& dbg_host = c->dbg_host;  // diagnostics heartbeat (host-mapped)
     if (c->debug_sync) {  // diagnostics: which kernel of the round does not finish
-      if (!dbg_host) HIPC(c, hipHostMalloc((void**)&dbg_host, sizeof(unsigned long long) * 8 * 4096, hipHostMallocMapped));
+      if (!dbg_host) HIPC(c, c->mem.renew_host(&dbg_host, 8 * 4096, hipHostMallocMapped));
       memset(dbg_host, 0, sizeof(unsigned long long) * 8 * 4096);
       HIPC(c, hipHostGetDevicePointer((void**)&a.dbg, dbg_host, 0));
       HIPC(c, hipStreamSynchronize(st));
@@ -2509,16 +2436,13 @@ static int ensure_defer(clrrt_ctx* c) {
     return fail(c, CLRRT_EINVAL, "defer_steps too small for sharded rounds (more than 256 rounds in flight)");
   if (!d.res || d.R < R) {
     HIPC(c, hipStreamSynchronize(c->stream));
-    for (void* p : {(void*)d.res, (void*)d.res_gb, (void*)d.cand, (void*)d.ncand, (void*)d.samp, (void*)d.best})
-      if (p) HIPC(c, hipFree(p));
-    d.res = nullptr; d.res_gb = nullptr; d.cand = nullptr; d.ncand = nullptr; d.samp = nullptr; d.best = nullptr;
     d.R = 0;
-    HIPC(c, dalloc(&d.res, (size_t)R * B * CAND_K));
-    HIPC(c, dalloc(&d.res_gb, (size_t)R * B * CAND_K));
-    HIPC(c, dalloc(&d.cand, (size_t)R * B * CAND_K));
-    HIPC(c, dalloc(&d.ncand, (size_t)R * B));
-    HIPC(c, dalloc(&d.samp, (size_t)R * B));
-    HIPC(c, dalloc(&d.best, (size_t)R * B));
+    HIPC(c, c->mem.renew(&d.res, (size_t)R * B * CAND_K));
+    HIPC(c, c->mem.renew(&d.res_gb, (size_t)R * B * CAND_K));
+    HIPC(c, c->mem.renew(&d.cand, (size_t)R * B * CAND_K));
+    HIPC(c, c->mem.renew(&d.ncand, (size_t)R * B));
+    HIPC(c, c->mem.renew(&d.samp, (size_t)R * B));
+    HIPC(c, c->mem.renew(&d.best, (size_t)R * B));
     d.R = R;
   }
   if (!d.gv || d.vcap < (int64_t)d.R * B) {
@@ -2528,37 +2452,28 @@ static int ensure_defer(clrrt_ctx* c) {
     int rc = flush_replays(c);  // rep_buf is re-made below
     if (rc != CLRRT_OK) return rc;
     HIPC(c, hipStreamSynchronize(c->stream));
-    for (void* p : {(void*)c->regnodes, (void*)c->gbnodes, (void*)c->so, (void*)c->out_nodes, (void*)c->jobs,
-                    c->rep_buf, (void*)c->cmp.packed, (void*)c->cmp.scanned, c->cmp.tmp})
-      if (p) HIPC(c, hipFree(p));
-    c->regnodes = nullptr; c->gbnodes = nullptr; c->so = nullptr; c->out_nodes = nullptr; c->jobs = nullptr;
-    c->rep_buf = nullptr; c->cmp.packed = nullptr; c->cmp.scanned = nullptr; c->cmp.tmp = nullptr;
-    for (void* p : {(void*)d.dlist[0], (void*)d.dlist[1], (void*)d.gv, (void*)d.pend, d.sel_tmp, (void*)d.d_cnt,
-                    d.carry[0], d.carry[1]})
-      if (p) HIPC(c, hipFree(p));
-    d.dlist[0] = d.dlist[1] = nullptr; d.gv = nullptr; d.pend = nullptr; d.sel_tmp = nullptr; d.d_cnt = nullptr;
-    d.carry[0] = d.carry[1] = nullptr;
-    HIPC(c, dalloc(&c->regnodes, V));
-    HIPC(c, dalloc(&c->gbnodes, V));
-    HIPC(c, dalloc(&c->so, V));
-    HIPC(c, dalloc(&c->out_nodes, 2 * V));
-    HIPC(c, dalloc(&c->jobs, 2 * V));
-    HIPC(c, hipMalloc(&c->rep_buf, replay_bytes() * (size_t)2 * V));
-    HIPC(c, dalloc(&c->cmp.packed, V));
-    HIPC(c, dalloc(&c->cmp.scanned, V));
+    d.vcap = 0;
+    HIPC(c, c->mem.renew(&c->regnodes, V));
+    HIPC(c, c->mem.renew(&c->gbnodes, V));
+    HIPC(c, c->mem.renew(&c->so, V));
+    HIPC(c, c->mem.renew(&c->out_nodes, 2 * V));
+    HIPC(c, c->mem.renew(&c->jobs, 2 * V));
+    HIPC(c, c->mem.renew_bytes(&c->rep_buf, replay_bytes() * (size_t)2 * V));
+    HIPC(c, c->mem.renew(&c->cmp.packed, V));
+    HIPC(c, c->mem.renew(&c->cmp.scanned, V));
     c->cmp.tmp_bytes = compact_scan_bytes((int)V);
-    HIPC(c, hipMalloc(&c->cmp.tmp, std::max<size_t>(c->cmp.tmp_bytes, 256)));
-    HIPC(c, dalloc(&d.dlist[0], V));
-    HIPC(c, dalloc(&d.dlist[1], V));
-    HIPC(c, dalloc(&d.gv, V));
-    HIPC(c, dalloc(&d.pend, V));
+    HIPC(c, c->mem.renew_bytes(&c->cmp.tmp, std::max<size_t>(c->cmp.tmp_bytes, 256)));
+    HIPC(c, c->mem.renew(&d.dlist[0], V));
+    HIPC(c, c->mem.renew(&d.dlist[1], V));
+    HIPC(c, c->mem.renew(&d.gv, V));
+    HIPC(c, c->mem.renew(&d.pend, V));
     d.sel_bytes = defer_select_bytes((int)V);
-    HIPC(c, hipMalloc(&d.sel_tmp, std::max<size_t>(d.sel_bytes, 256)));
-    HIPC(c, dalloc(&d.d_cnt, 3));
+    HIPC(c, c->mem.renew_bytes(&d.sel_tmp, std::max<size_t>(d.sel_bytes, 256)));
+    HIPC(c, c->mem.renew(&d.d_cnt, 3));
     // suspended chains: at most every job of the rounds in flight (a launch's chains all come from them)
     d.carry_cap = (int)std::min<int64_t>(V * CAND_K, 1 << 21);
-    HIPC(c, hipMalloc(&d.carry[0], carry_bytes() * (size_t)d.carry_cap));
-    HIPC(c, hipMalloc(&d.carry[1], carry_bytes() * (size_t)d.carry_cap));
+    HIPC(c, c->mem.renew_bytes(&d.carry[0], carry_bytes() * (size_t)d.carry_cap));
+    HIPC(c, c->mem.renew_bytes(&d.carry[1], carry_bytes() * (size_t)d.carry_cap));
     d.vcap = V;
   }
   return CLRRT_OK;
@@ -2594,10 +2509,8 @@ static int ensure_slots(clrrt_ctx* c) {
   if (c->slots && c->slot_rows >= need) return CLRRT_OK;
   HIPC(c, hipSetDevice(c->device));
   HIPC(c, hipStreamSynchronize(c->stream));
-  if (c->slots) HIPC(c, hipFree(c->slots));
-  c->slots = nullptr;
   c->slot_rows = 0;
-  HIPC(c, dalloc(&c->slots, (size_t)2 * need * 10 * c->cap.max_batch * CAND_K));
+  HIPC(c, c->mem.renew(&c->slots, (size_t)2 * need * 10 * c->cap.max_batch * CAND_K));
   c->slot_rows = need;
   return CLRRT_OK;
 }
@@ -2868,13 +2781,10 @@ int clrrt_nn_merge(clrrt_ctx* c, int32_t n, int32_t parts, const int32_t* ids, c
   const int64_t pairs = (int64_t)parts * n;
   if (pairs > c->pm_cap) {
     HIPC(c, hipStreamSynchronize(st));
-    for (void* p : {(void*)c->pm_ids, (void*)c->pm_keys, (void*)c->pm_counts})
-      if (p) HIPC(c, hipFree(p));
-    c->pm_ids = nullptr; c->pm_keys = nullptr; c->pm_counts = nullptr;
     c->pm_cap = 0;
-    HIPC(c, dalloc(&c->pm_ids, pairs * CAND_K));
-    HIPC(c, dalloc(&c->pm_keys, pairs * CAND_K));
-    HIPC(c, dalloc(&c->pm_counts, pairs));
+    HIPC(c, c->mem.renew(&c->pm_ids, pairs * CAND_K));
+    HIPC(c, c->mem.renew(&c->pm_keys, pairs * CAND_K));
+    HIPC(c, c->mem.renew(&c->pm_counts, pairs));
     c->pm_cap = pairs;
   }
   HIPC(c, hipMemcpyAsync(c->pm_ids, ids, sizeof(int) * CAND_K * pairs, hipMemcpyDefault, st));
@@ -2899,7 +2809,7 @@ int clrrt_round_eval_lists(clrrt_ctx* c, const clrrt_sample* samples, int32_t n,
   pf_discard(c);  // a prefetched search is for the engine's own lists
   ListSet& cur = *c->ls[0];
   hipStream_t st = c->stream;
-  if (!c->d_bad) HIPC(c, dalloc(&c->d_bad, 1));
+  if (!c->d_bad) HIPC(c, c->mem.renew(&c->d_bad, 1));
   memcpy(cur.h_samples, samples, sizeof(clrrt_sample) * n);
   HIPC(c, hipMemcpyAsync(cur.d_samples, cur.h_samples, sizeof(clrrt_sample) * n, hipMemcpyHostToDevice, st));
   HIPC(c, hipMemcpyAsync(cur.cand, ids, sizeof(int) * CAND_K * n, hipMemcpyDefault, st));
@@ -3035,14 +2945,12 @@ static int commit_round(clrrt_ctx* c, int nn, double elapsed_ms, int* n_app) {
   if (n_all > 0) {
     if (n_all > h.xcap) {
       HIPC(c, hipStreamSynchronize(c->stream));
-      for (void* p : {(void*)h.xbuf, (void*)h.xkey, h.xtmp})
-        if (p) HIPC(c, hipFree(p));
-      h.xbuf = nullptr; h.xkey = nullptr; h.xtmp = nullptr;
+      h.xcap = 0;
       const int64_t cap = std::max<int64_t>(2 * (int64_t)n_all, 4096);
-      HIPC(c, dalloc(&h.xbuf, cap));
-      HIPC(c, dalloc(&h.xkey, 4 * cap));
+      HIPC(c, c->mem.renew(&h.xbuf, cap));
+      HIPC(c, c->mem.renew(&h.xkey, 4 * cap));
       h.xtmp_bytes = xorder_sort_bytes((int)cap);
-      HIPC(c, hipMalloc(&h.xtmp, std::max<size_t>(h.xtmp_bytes, 256)));
+      HIPC(c, c->mem.renew_bytes(&h.xtmp, std::max<size_t>(h.xtmp_bytes, 256)));
       h.xcap = cap;
     }
     HIPC(c, launch_xorder(c->stream, (const clrrt_node*)all, n_all, c->def.active, h.xkey, h.xtmp, h.xtmp_bytes,
@@ -3077,16 +2985,18 @@ struct LagSlot {
 };
 
 static int lag_alloc(clrrt_ctx* c) {
-  if (c->side2) return CLRRT_OK;
+  if (c->nn_order) return CLRRT_OK;
   const int64_t B = c->cap.max_batch;
-  HIPC(c, alloc_lists(c->sets[2], B));
+  int rc = alloc_lists(c, c->sets[2], B);
+  if (rc != CLRRT_OK) return rc;
   for (ListSet& s : c->sets) {
-    for (hipEvent_t* e : {&s.ev, &s.evw, &s.evm}) HIPC(c, hipEventCreateWithFlags(e, hipEventDisableTiming));
-    HIPC(c, dalloc(&s.wseed, B));
+    for (hipEvent_t* e : {&s.ev, &s.evw, &s.evm})
+      if (!*e) HIPC(c, hipEventCreateWithFlags(e, hipEventDisableTiming));
+    HIPC(c, c->mem.renew(&s.wseed, B));
   }
-  HIPC(c, hipStreamCreateWithFlags(&c->side2, hipStreamNonBlocking));
-  HIPC(c, hipStreamCreateWithFlags(&c->mst, hipStreamNonBlocking));
-  HIPC(c, dalloc(&c->nn_order, B));
+  if (!c->side2) HIPC(c, hipStreamCreateWithFlags(&c->side2, hipStreamNonBlocking));
+  if (!c->mst) HIPC(c, hipStreamCreateWithFlags(&c->mst, hipStreamNonBlocking));
+  HIPC(c, c->mem.renew(&c->nn_order, B));  // last: marks the lag-2 members complete
   return CLRRT_OK;
 }
 
@@ -3097,30 +3007,30 @@ static int alloc_walk_delta(clrrt_ctx* c) {
   if (!w.P) {
     const int64_t cap = walk_delta_cap(c->cap.max_nodes, c->cap.max_batch);
     const int64_t Mp = walk_tile_count(cap) * 32;  // the padded records
-    HIPC(c, dalloc(&w.keys, 2 * cap));
-    HIPC(c, dalloc(&w.vals, cap));
+    HIPC(c, c->mem.renew(&w.keys, 2 * cap));
+    HIPC(c, c->mem.renew(&w.vals, cap));
     w.tmp_bytes = walk_sort_bytes((int)cap);
-    HIPC(c, hipMalloc(&w.tmp, std::max<size_t>(w.tmp_bytes, 256)));
-    HIPC(c, dalloc(&w.skeys, cap));
-    HIPC(c, dalloc(&w.sids, cap));
-    HIPC(c, dalloc(&w.Q, Mp));
-    HIPC(c, dalloc(&w.CE, Mp));
-    HIPC(c, dalloc(&w.ID, Mp));
-    HIPC(c, dalloc(&w.HEAD, Mp));
-    HIPC(c, dalloc(&w.trun, walk_tile_count(cap)));
-    HIPC(c, dalloc(&w.tiles, walk_tile_count(cap)));
-    HIPC(c, dalloc(&w.supers, walk_super_count(cap)));
+    HIPC(c, c->mem.renew_bytes(&w.tmp, std::max<size_t>(w.tmp_bytes, 256)));
+    HIPC(c, c->mem.renew(&w.skeys, cap));
+    HIPC(c, c->mem.renew(&w.sids, cap));
+    HIPC(c, c->mem.renew(&w.Q, Mp));
+    HIPC(c, c->mem.renew(&w.CE, Mp));
+    HIPC(c, c->mem.renew(&w.ID, Mp));
+    HIPC(c, c->mem.renew(&w.HEAD, Mp));
+    HIPC(c, c->mem.renew(&w.trun, walk_tile_count(cap)));
+    HIPC(c, c->mem.renew(&w.tiles, walk_tile_count(cap)));
+    HIPC(c, c->mem.renew(&w.supers, walk_super_count(cap)));
     w.sorted_n = -1;
     w.cap_nodes = cap;
     w.cap_batch = (int)c->cap.max_batch;
-    HIPC(c, dalloc(&w.P, Mp));  // last: marks the set complete
+    HIPC(c, c->mem.renew(&w.P, Mp));  // last: marks the set complete
   }
   w.index_kind = c->nnw_index;
   w.hscale_pct = c->nnw_hscale;
   if (c->nn_delta_verify && !c->vseed) {
-    HIPC(c, dalloc(&c->vpk, c->partial_cap));
-    HIPC(c, dalloc(&c->vpi, c->partial_cap));
-    HIPC(c, dalloc(&c->vseed, c->cap.max_batch));
+    HIPC(c, c->mem.renew(&c->vpk, c->partial_cap));
+    HIPC(c, c->mem.renew(&c->vpi, c->partial_cap));
+    HIPC(c, c->mem.renew(&c->vseed, c->cap.max_batch));
   }
   return CLRRT_OK;
 }
@@ -3583,7 +3493,7 @@ int clrrt_set_shards(clrrt_ctx* c, int32_t rank, int32_t world, void* dev_local,
   h.fn = on ? exchange : nullptr;
   h.user = on ? user : nullptr;
   c->rank = rank;  // owner of this rank's records
-  if (on && !h.d_goal) HIPC(c, dalloc(&h.d_goal, 1));
+  if (on && !h.d_goal) HIPC(c, c->mem.renew(&h.d_goal, 1));
   return CLRRT_OK;
 }
 
@@ -3602,30 +3512,28 @@ int clrrt_rollout_batch(clrrt_ctx* c, const clrrt_rollout_job* jobs, int32_t n, 
     hj[j].sx = jobs[j].sample[0]; hj[j].sy = jobs[j].sample[1];
     hj[j].row_off = rows_out ? (int64_t)j * rows_cap : -1;
   }
-  Job* dj = nullptr;
-  RollRes* dr = nullptr;
-  double* drows = nullptr;
-  hipError_t e = hipMalloc((void**)&dj, sizeof(Job) * n);
-  if (e == hipSuccess) e = hipMalloc((void**)&dr, sizeof(RollRes) * n);
-  if (e == hipSuccess && rows_out) e = hipMalloc((void**)&drows, sizeof(double) * 10 * (size_t)rows_cap * n);
-  if (e == hipSuccess) e = hipMemcpyAsync(dj, hj.data(), sizeof(Job) * n, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) {
+  const char* const pre = "rollout_batch: ";
+  std::vector<RollRes> hr(n);  // (before the scratch: outlives its frees, which drain the copies into it)
+  Scratch<Job> dj;
+  Scratch<RollRes> dr;
+  Scratch<double> drows;
+  HIPP(c, pre, dj.alloc(n));
+  HIPP(c, pre, dr.alloc(n));
+  if (rows_out) HIPP(c, pre, drows.alloc(10 * (size_t)rows_cap * n));
+  HIPP(c, pre, hipMemcpyAsync(dj, hj.data(), sizeof(Job) * n, hipMemcpyHostToDevice, c->stream));
+  {
     RollArgs a = roll_args(c, n);
     a.jobs = dj;
     a.arena = drows;
     a.res = dr;
     KTimer kt(c, 1);
-    e = launch_rollout(c->stream, SRC_LIST, a);
+    HIPP(c, pre, launch_rollout(c->stream, SRC_LIST, a));
   }
-  std::vector<RollRes> hr(n);
-  if (e == hipSuccess) e = hipMemcpyAsync(hr.data(), dr, sizeof(RollRes) * n, hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess && rows_out)
-    e = hipMemcpyAsync(rows_out, drows, sizeof(double) * 10 * (size_t)rows_cap * n, hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  hipFree(dj);
-  hipFree(dr);
-  if (drows) hipFree(drows);
-  if (e != hipSuccess) return fail(c, CLRRT_EHIP, std::string("rollout_batch: ") + hipGetErrorString(e));
+  HIPP(c, pre, hipMemcpyAsync(hr.data(), dr, sizeof(RollRes) * n, hipMemcpyDeviceToHost, c->stream));
+  if (rows_out)
+    HIPP(c, pre, hipMemcpyAsync(rows_out, drows, sizeof(double) * 10 * (size_t)rows_cap * n, hipMemcpyDeviceToHost,
+                                c->stream));
+  HIPP(c, pre, hipStreamSynchronize(c->stream));
   for (int j = 0; j < n; j++) {
     clrrt_rollout_result& o = out[j];
     memset(&o, 0, sizeof(o));
@@ -3660,15 +3568,17 @@ int clrrt_simulate(clrrt_ctx* c, const clrrt_sim_case* cases, int32_t n, clrrt_r
     s.row_off = rows_out ? (int64_t)j * rows_cap : -1;
     s.ref_off = ref_out ? (int64_t)j * 3 * ref_cap : -1;
   }
-  SimJob* dj = nullptr;
-  RollRes* dr = nullptr;
-  double *drows = nullptr, *dref = nullptr;
-  hipError_t e = hipMalloc((void**)&dj, sizeof(SimJob) * n);
-  if (e == hipSuccess) e = hipMalloc((void**)&dr, sizeof(RollRes) * n);
-  if (e == hipSuccess && rows_out) e = hipMalloc((void**)&drows, sizeof(double) * 10 * (size_t)rows_cap * n);
-  if (e == hipSuccess && ref_out) e = hipMalloc((void**)&dref, sizeof(double) * 3 * (size_t)ref_cap * n);
-  if (e == hipSuccess) e = hipMemcpyAsync(dj, hj.data(), sizeof(SimJob) * n, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) {
+  const char* const pre = "simulate: ";
+  std::vector<RollRes> hr(n);  // (before the scratch: outlives its frees, which drain the copies into it)
+  Scratch<SimJob> dj;
+  Scratch<RollRes> dr;
+  Scratch<double> drows, dref;
+  HIPP(c, pre, dj.alloc(n));
+  HIPP(c, pre, dr.alloc(n));
+  if (rows_out) HIPP(c, pre, drows.alloc(10 * (size_t)rows_cap * n));
+  if (ref_out) HIPP(c, pre, dref.alloc(3 * (size_t)ref_cap * n));
+  HIPP(c, pre, hipMemcpyAsync(dj, hj.data(), sizeof(SimJob) * n, hipMemcpyHostToDevice, c->stream));
+  {
     RollArgs a = roll_args(c, n);
     a.sims = dj;
     a.arena = drows;
@@ -3676,20 +3586,16 @@ int clrrt_simulate(clrrt_ctx* c, const clrrt_sim_case* cases, int32_t n, clrrt_r
     a.ref_cap = ref_cap;
     a.res = dr;
     KTimer kt(c, 1);
-    e = launch_rollout(c->stream, SRC_EXPL, a);
+    HIPP(c, pre, launch_rollout(c->stream, SRC_EXPL, a));
   }
-  std::vector<RollRes> hr(n);
-  if (e == hipSuccess) e = hipMemcpyAsync(hr.data(), dr, sizeof(RollRes) * n, hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess && rows_out)
-    e = hipMemcpyAsync(rows_out, drows, sizeof(double) * 10 * (size_t)rows_cap * n, hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess && ref_out)
-    e = hipMemcpyAsync(ref_out, dref, sizeof(double) * 3 * (size_t)ref_cap * n, hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  hipFree(dj);
-  hipFree(dr);
-  if (drows) hipFree(drows);
-  if (dref) hipFree(dref);
-  if (e != hipSuccess) return fail(c, CLRRT_EHIP, std::string("simulate: ") + hipGetErrorString(e));
+  HIPP(c, pre, hipMemcpyAsync(hr.data(), dr, sizeof(RollRes) * n, hipMemcpyDeviceToHost, c->stream));
+  if (rows_out)
+    HIPP(c, pre, hipMemcpyAsync(rows_out, drows, sizeof(double) * 10 * (size_t)rows_cap * n, hipMemcpyDeviceToHost,
+                                c->stream));
+  if (ref_out)
+    HIPP(c, pre, hipMemcpyAsync(ref_out, dref, sizeof(double) * 3 * (size_t)ref_cap * n, hipMemcpyDeviceToHost,
+                                c->stream));
+  HIPP(c, pre, hipStreamSynchronize(c->stream));
   for (int j = 0; j < n; j++) {
     clrrt_rollout_result& o = out[j];
     memset(&o, 0, sizeof(o));
@@ -3709,19 +3615,16 @@ int clrrt_selftest_math(clrrt_ctx* c, int32_t fn, const double* a, const double*
   if (!c || n < 0 || (n > 0 && (!a || !b || !out)) || fn < 0 || fn > 28) return CLRRT_EINVAL;
   HIPC(c, hipSetDevice(c->device));
   if (n == 0) return CLRRT_OK;
-  double *da = nullptr, *db = nullptr, *dout = nullptr;
-  hipError_t e = hipMalloc((void**)&da, sizeof(double) * n);
-  if (e == hipSuccess) e = hipMalloc((void**)&db, sizeof(double) * n);
-  if (e == hipSuccess) e = hipMalloc((void**)&dout, sizeof(double) * n);
-  if (e == hipSuccess) e = hipMemcpyAsync(da, a, sizeof(double) * n, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(db, b, sizeof(double) * n, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = launch_selftest_math(c->stream, fn, da, db, n, dout);
-  if (e == hipSuccess) e = hipMemcpyAsync(out, dout, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  hipFree(da);
-  hipFree(db);
-  hipFree(dout);
-  if (e != hipSuccess) return fail(c, CLRRT_EHIP, std::string("selftest_math: ") + hipGetErrorString(e));
+  const char* const pre = "selftest_math: ";
+  Scratch<double> da, db, dout;
+  HIPP(c, pre, da.alloc(n));
+  HIPP(c, pre, db.alloc(n));
+  HIPP(c, pre, dout.alloc(n));
+  HIPP(c, pre, hipMemcpyAsync(da, a, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
+  HIPP(c, pre, hipMemcpyAsync(db, b, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
+  HIPP(c, pre, launch_selftest_math(c->stream, fn, da, db, n, dout));
+  HIPP(c, pre, hipMemcpyAsync(out, dout, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
+  HIPP(c, pre, hipStreamSynchronize(c->stream));
   return CLRRT_OK;
 }
 
@@ -3729,17 +3632,15 @@ int clrrt_obstacle_distance(clrrt_ctx* c, const double* states, int32_t n, doubl
   if (!c || n < 0 || (n > 0 && (!states || !out))) return CLRRT_EINVAL;
   HIPC(c, hipSetDevice(c->device));
   if (n == 0) return CLRRT_OK;
-  double *din = nullptr, *dout = nullptr;
-  hipError_t e = hipMalloc((void**)&din, sizeof(double) * 10 * (size_t)n);
-  if (e == hipSuccess) e = hipMalloc((void**)&dout, sizeof(double) * (size_t)n);
-  if (e == hipSuccess) e = hipMemcpyAsync(din, states, sizeof(double) * 10 * (size_t)n, hipMemcpyHostToDevice, c->stream);
+  const char* const pre = "obstacle_distance: ";
+  Scratch<double> din, dout;
+  HIPP(c, pre, din.alloc(10 * (size_t)n));
+  HIPP(c, pre, dout.alloc(n));
+  HIPP(c, pre, hipMemcpyAsync(din, states, sizeof(double) * 10 * (size_t)n, hipMemcpyHostToDevice, c->stream));
   const OccGrid og = occ_view(c);
-  if (e == hipSuccess) e = launch_obs_distance(c->stream, c->dp, c->obs, din, n, dout, &og);
-  if (e == hipSuccess) e = hipMemcpyAsync(out, dout, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  hipFree(din);
-  hipFree(dout);
-  if (e != hipSuccess) return fail(c, CLRRT_EHIP, std::string("obstacle_distance: ") + hipGetErrorString(e));
+  HIPP(c, pre, launch_obs_distance(c->stream, c->dp, c->obs, din, n, dout, &og));
+  HIPP(c, pre, hipMemcpyAsync(out, dout, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  HIPP(c, pre, hipStreamSynchronize(c->stream));
   return CLRRT_OK;
 }
 
@@ -3776,27 +3677,23 @@ int clrrt_selftest_units(clrrt_ctx* c, int32_t unit, const double* in, int32_t n
       derive(q, cps[i], c->n_obs);
     }
   }
-  double *din = nullptr, *dout = nullptr;
-  BakedObs* dobs = nullptr;
-  DevParams* dcp = nullptr;
-  hipError_t e = hipMalloc((void**)&din, sizeof(double) * nin);
-  if (e == hipSuccess) e = hipMalloc((void**)&dout, sizeof(double) * nout);
-  if (e == hipSuccess && !baked.empty()) e = hipMalloc((void**)&dobs, sizeof(BakedObs) * baked.size());
-  if (e == hipSuccess && !cps.empty()) e = hipMalloc((void**)&dcp, sizeof(DevParams) * cps.size());
-  if (e == hipSuccess) e = hipMemcpyAsync(din, in, sizeof(double) * nin, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess && dobs)
-    e = hipMemcpyAsync(dobs, baked.data(), sizeof(BakedObs) * baked.size(), hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess && dcp)
-    e = hipMemcpyAsync(dcp, cps.data(), sizeof(DevParams) * cps.size(), hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(dout, 0, sizeof(double) * nout, c->stream);
-  if (e == hipSuccess) e = launch_selftest_units(c->stream, unit, din, dobs, n, c->dp, dcp, dout);
-  if (e == hipSuccess) e = hipMemcpyAsync(out, dout, sizeof(double) * nout, hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  hipFree(din);
-  hipFree(dout);
-  if (dobs) hipFree(dobs);
-  if (dcp) hipFree(dcp);
-  if (e != hipSuccess) return fail(c, CLRRT_EHIP, std::string("selftest_units: ") + hipGetErrorString(e));
+  const char* const pre = "selftest_units: ";
+  Scratch<double> din, dout;
+  Scratch<BakedObs> dobs;
+  Scratch<DevParams> dcp;
+  HIPP(c, pre, din.alloc(nin));
+  HIPP(c, pre, dout.alloc(nout));
+  if (!baked.empty()) HIPP(c, pre, dobs.alloc(baked.size()));
+  if (!cps.empty()) HIPP(c, pre, dcp.alloc(cps.size()));
+  HIPP(c, pre, hipMemcpyAsync(din, in, sizeof(double) * nin, hipMemcpyHostToDevice, c->stream));
+  if (dobs)
+    HIPP(c, pre, hipMemcpyAsync(dobs, baked.data(), sizeof(BakedObs) * baked.size(), hipMemcpyHostToDevice, c->stream));
+  if (dcp)
+    HIPP(c, pre, hipMemcpyAsync(dcp, cps.data(), sizeof(DevParams) * cps.size(), hipMemcpyHostToDevice, c->stream));
+  HIPP(c, pre, hipMemsetAsync(dout, 0, sizeof(double) * nout, c->stream));
+  HIPP(c, pre, launch_selftest_units(c->stream, unit, din, dobs, n, c->dp, dcp, dout));
+  HIPP(c, pre, hipMemcpyAsync(out, dout, sizeof(double) * nout, hipMemcpyDeviceToHost, c->stream));
+  HIPP(c, pre, hipStreamSynchronize(c->stream));
   return CLRRT_OK;
 }
 
@@ -3812,24 +3709,20 @@ int clrrt_selftest_collision(clrrt_ctx* c, int32_t path, const double* states, c
     return fail(c, CLRRT_EINVAL, "selftest_collision: a rollout launch would not use the cooperative check here");
   HIPC(c, hipSetDevice(c->device));
   if (n == 0) return CLRRT_OK;
-  double *din = nullptr, *ddist = nullptr;
-  int32_t* dact = nullptr;
-  uint32_t* dtests = nullptr;
-  hipError_t e = hipMalloc((void**)&din, sizeof(double) * 10 * (size_t)n);
-  if (e == hipSuccess) e = hipMalloc((void**)&ddist, sizeof(double) * (size_t)n);
-  if (e == hipSuccess) e = hipMalloc((void**)&dact, sizeof(int32_t) * (size_t)n);
-  if (e == hipSuccess) e = hipMalloc((void**)&dtests, sizeof(uint32_t) * (size_t)n);
-  if (e == hipSuccess) e = hipMemcpyAsync(din, states, sizeof(double) * 10 * (size_t)n, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(dact, active, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = launch_selftest_collision(c->stream, a, path, din, dact, n, ddist, dtests);
-  if (e == hipSuccess) e = hipMemcpyAsync(dist, ddist, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(tests, dtests, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  hipFree(din);
-  hipFree(ddist);
-  hipFree(dact);
-  hipFree(dtests);
-  if (e != hipSuccess) return fail(c, CLRRT_EHIP, std::string("selftest_collision: ") + hipGetErrorString(e));
+  const char* const pre = "selftest_collision: ";
+  Scratch<double> din, ddist;
+  Scratch<int32_t> dact;
+  Scratch<uint32_t> dtests;
+  HIPP(c, pre, din.alloc(10 * (size_t)n));
+  HIPP(c, pre, ddist.alloc(n));
+  HIPP(c, pre, dact.alloc(n));
+  HIPP(c, pre, dtests.alloc(n));
+  HIPP(c, pre, hipMemcpyAsync(din, states, sizeof(double) * 10 * (size_t)n, hipMemcpyHostToDevice, c->stream));
+  HIPP(c, pre, hipMemcpyAsync(dact, active, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+  HIPP(c, pre, launch_selftest_collision(c->stream, a, path, din, dact, n, ddist, dtests));
+  HIPP(c, pre, hipMemcpyAsync(dist, ddist, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  HIPP(c, pre, hipMemcpyAsync(tests, dtests, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  HIPP(c, pre, hipStreamSynchronize(c->stream));
   return CLRRT_OK;
 }
 
@@ -3898,13 +3791,12 @@ int clrrt_walk_audit(clrrt_ctx* c, const clrrt_sample* samples, int32_t n, int32
   HIPC(c, hipMemcpyAsync(cur.d_samples, cur.h_samples, sizeof(clrrt_sample) * n, hipMemcpyHostToDevice, c->stream));
   c->nnw_built.n = -1;
   HIPC(c, launch_nn_walk_build(c->stream, c->nn, (int)c->n_nodes, su.fr, su.x0, su.y0, su.x1, su.y1, c->nnw));
-  int* d_out = nullptr;
-  HIPC(c, hipMalloc(&d_out, sizeof(int32_t) * 20 * (size_t)n));
-  hipError_t e = launch_walk_audit(c->stream, cur.d_samples, n, c->nn, (int)c->n_nodes, c->dp, su.fr, c->nnw, d_out);
-  if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, sizeof(int32_t) * 20 * (size_t)n, hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  hipFree(d_out);
-  if (e != hipSuccess) return fail(c, CLRRT_EHIP, std::string("clrrt_walk_audit: ") + hipGetErrorString(e));
+  const char* const pre = "clrrt_walk_audit: ";
+  Scratch<int> d_out;
+  HIPC(c, d_out.alloc(20 * (size_t)n));  // (HIPC, not HIPP: this failure never carried the prefix)
+  HIPP(c, pre, launch_walk_audit(c->stream, cur.d_samples, n, c->nn, (int)c->n_nodes, c->dp, su.fr, c->nnw, d_out));
+  HIPP(c, pre, hipMemcpyAsync(out, d_out, sizeof(int32_t) * 20 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  HIPP(c, pre, hipStreamSynchronize(c->stream));
   return CLRRT_OK;
 }
 

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/clrrt_xchg.h"
+#include "clrrt_devmem_hip.hpp"
 #include "clrrt_rendezvous.hpp"
 
 namespace {
@@ -266,6 +267,7 @@ struct clrrt_xchg_group {
 
 struct clrrt_xchg {
   int rank = 0, world = 1, device = 0;
+  clrrt::DevMem<HipMem> mem;  // every device and pinned buffer below is its (freed by clrrt_xchg_destroy)
   int64_t cap = 0;    // record rows of the send buffer (besides the header row)
   int64_t bound = 0;  // rows of the first gather
   char* send = nullptr;     // [cap + 1] rows
@@ -301,16 +303,16 @@ namespace {
 int alloc_common(clrrt_xchg* x) {
   const size_t part = (size_t)(x->cap + 1) * ROW;
   XHIP(hipSetDevice(x->device));
-  XHIP(hipMalloc((void**)&x->send, part));
+  XHIP(x->mem.renew(&x->send, part));
   XHIP(hipMemset(x->send, 0, part));
-  XHIP(hipMalloc((void**)&x->recv, part * x->world));
-  XHIP(hipMalloc((void**)&x->out, (size_t)x->cap * ROW * x->world));
-  XHIP(hipMalloc((void**)&x->d_sum, sizeof(Summary)));
-  XHIP(hipHostMalloc((void**)&x->h_sum, sizeof(Summary), hipHostMallocDefault));
-  XHIP(hipHostMalloc((void**)&x->h_hdr, sizeof(Header), hipHostMallocDefault));
+  XHIP(x->mem.renew(&x->recv, part * x->world));
+  XHIP(x->mem.renew(&x->out, (size_t)x->cap * ROW * x->world));
+  XHIP(x->mem.renew(&x->d_sum, 1));
+  XHIP(x->mem.renew_host(&x->h_sum, 1));
+  XHIP(x->mem.renew_host(&x->h_hdr, 1));
   XHIP(hipEventCreateWithFlags(&x->ev_sum, hipEventDisableTiming));
-  XHIP(hipMalloc((void**)&x->d_phdr, sizeof(PathHdr) * (1 + x->world)));
-  XHIP(hipHostMalloc((void**)&x->h_phdr, sizeof(PathHdr) * (1 + x->world), hipHostMallocDefault));
+  XHIP(x->mem.renew(&x->d_phdr, 1 + x->world));
+  XHIP(x->mem.renew_host(&x->h_phdr, 1 + x->world));
   return CLRRT_OK;
 }
 
@@ -358,7 +360,7 @@ int run_exchange(clrrt_xchg* x, clrrt_exchange_io* io, hipStream_t st, bool copy
   if (s.n_all > INT32_MAX) return fail(CLRRT_ECAPACITY, "clrrt_xchg: more than 2^31 records in one round");
   if (s.max_count > x->bound && gather_excess) {
     const int64_t ex = s.max_count - x->bound;
-    if (!x->recv_ex) XHIP(hipMalloc((void**)&x->recv_ex, (size_t)x->cap * ROW * x->world));
+    if (!x->recv_ex) XHIP(x->mem.renew(&x->recv_ex, (size_t)x->cap * ROW * x->world));
     if ((rc = gather(1 + x->bound, ex, x->recv_ex, ex)) != CLRRT_OK) return rc;
     x->st[1]++;
     x->st[2]++;
@@ -453,10 +455,8 @@ struct PathView {
 int path_grow_recv(clrrt_xchg* x, int64_t rows) {
   if (rows * x->world <= x->p_recv_rows) return CLRRT_OK;
   const int64_t cap = std::max<int64_t>(rows * x->world, 2 * x->p_recv_rows);
-  if (x->p_recv) XHIP(hipFree(x->p_recv));  // (waits for the last completion's kernel)
-  x->p_recv = nullptr;
   x->p_recv_rows = 0;
-  XHIP(hipMalloc((void**)&x->p_recv, (size_t)cap * PROW));
+  XHIP(x->mem.renew(&x->p_recv, (size_t)cap * PROW));  // (the device free waits for the last completion's kernel)
   x->p_recv_rows = cap;
   return CLRRT_OK;
 }
@@ -591,10 +591,8 @@ int32_t clrrt_xchg_path_rows(void* user, clrrt_ctx* ctx, int64_t* rows_moved) {
   // the n headers, read once: the hash, the rows to take and the ranks they come from
   if (v.n > x->h_nodes_cap) {
     const int cap = std::max(v.n, std::max(64, 2 * x->h_nodes_cap));
-    if (x->h_nodes) XHIP(hipHostFree(x->h_nodes));
-    x->h_nodes = nullptr;
     x->h_nodes_cap = 0;
-    XHIP(hipHostMalloc((void**)&x->h_nodes, sizeof(clrrt_node) * cap, hipHostMallocDefault));
+    XHIP(x->mem.renew_host(&x->h_nodes, cap));
     x->h_nodes_cap = cap;
   }
   auto read_headers = [&]() -> int {
@@ -739,11 +737,7 @@ void clrrt_xchg_destroy(clrrt_xchg* x) {
     if (x->group->slot[x->rank].x == x) x->group->slot[x->rank].x = nullptr;
   }
   if (x->comm) (void)ncclCommDestroy(x->comm);
-  for (void* p : {(void*)x->send, (void*)x->recv, (void*)x->recv_ex, (void*)x->out, (void*)x->d_sum, (void*)x->p_recv,
-                  (void*)x->d_phdr})
-    if (p) (void)hipFree(p);
-  for (void* p : {(void*)x->h_sum, (void*)x->h_hdr, (void*)x->h_nodes, (void*)x->h_phdr})
-    if (p) (void)hipHostFree(p);
+  x->mem.release_all();
   for (hipEvent_t e : {x->ev_sum, x->ev_sent, x->ev_pulled})
     if (e) (void)hipEventDestroy(e);
   delete x;
@@ -779,39 +773,32 @@ int clrrt_xchg_selftest_concat(int32_t device, int32_t W, int32_t bound, const i
     memcpy(&hp[(size_t)r * stride * ROW], &h, sizeof(h));
   }
   XHIP(hipSetDevice(device));
-  char *dp = nullptr, *dx = nullptr, *dout = nullptr;
-  Summary* ds = nullptr;
+  Scratch<char> dp, dx, dout;
+  Scratch<Summary> ds;
   Summary hs;
-  auto run = [&]() -> int {
-    XHIP(hipMalloc((void**)&dp, hp.size()));
-    XHIP(hipMalloc((void**)&dx, std::max<size_t>(hx.size(), 16)));
-    XHIP(hipMalloc((void**)&dout, std::max<size_t>((size_t)total * ROW, 16)));
-    XHIP(hipMalloc((void**)&ds, sizeof(Summary)));
-    XHIP(hipMemcpy(dp, hp.data(), hp.size(), hipMemcpyHostToDevice));
-    if (!hx.empty()) XHIP(hipMemcpy(dx, hx.data(), hx.size(), hipMemcpyHostToDevice));
-    XHIP(hipMemset(dout, 0, std::max<size_t>((size_t)total * ROW, 16)));
-    ConcatArgs a{};
-    a.parts = (const uint4*)dp;
-    a.excess = excess_rows > 0 ? (const uint4*)dx : nullptr;
-    a.out = (uint4*)dout;
-    a.summary = ds;
-    a.part_stride = stride;
-    a.ex_stride = a.ex_rows = excess_rows;
-    a.out_cap = total;
-    a.cap_rows = (int64_t)bound + excess_rows;
-    a.W = W;
-    a.bound = bound;
-    a.copy_first = a.copy_excess = 1;
-    XHIP(launch_concat(nullptr, a, (int64_t)bound + excess_rows));
-    XHIP(hipDeviceSynchronize());
-    if (total > 0) XHIP(hipMemcpy(out_rows, dout, (size_t)total * ROW, hipMemcpyDeviceToHost));
-    XHIP(hipMemcpy(&hs, ds, sizeof(hs), hipMemcpyDeviceToHost));
-    return CLRRT_OK;
-  };
-  const int rc = run();
-  for (void* p : {(void*)dp, (void*)dx, (void*)dout, (void*)ds})
-    if (p) (void)hipFree(p);
-  if (rc != CLRRT_OK) return rc;
+  XHIP(dp.alloc(hp.size()));
+  XHIP(dx.alloc(std::max<size_t>(hx.size(), 16)));
+  XHIP(dout.alloc(std::max<size_t>((size_t)total * ROW, 16)));
+  XHIP(ds.alloc(1));
+  XHIP(hipMemcpy(dp, hp.data(), hp.size(), hipMemcpyHostToDevice));
+  if (!hx.empty()) XHIP(hipMemcpy(dx, hx.data(), hx.size(), hipMemcpyHostToDevice));
+  XHIP(hipMemset(dout, 0, std::max<size_t>((size_t)total * ROW, 16)));
+  ConcatArgs a{};
+  a.parts = (const uint4*)dp.p;
+  a.excess = excess_rows > 0 ? (const uint4*)dx.p : nullptr;
+  a.out = (uint4*)dout.p;
+  a.summary = ds;
+  a.part_stride = stride;
+  a.ex_stride = a.ex_rows = excess_rows;
+  a.out_cap = total;
+  a.cap_rows = (int64_t)bound + excess_rows;
+  a.W = W;
+  a.bound = bound;
+  a.copy_first = a.copy_excess = 1;
+  XHIP(launch_concat(nullptr, a, (int64_t)bound + excess_rows));
+  XHIP(hipDeviceSynchronize());
+  if (total > 0) XHIP(hipMemcpy(out_rows, dout, (size_t)total * ROW, hipMemcpyDeviceToHost));
+  XHIP(hipMemcpy(&hs, ds, sizeof(hs), hipMemcpyDeviceToHost));
   summary[0] = hs.n_all;
   summary[1] = hs.max_count;
   memcpy(&summary[2], &hs.max_elapsed, 8);
@@ -855,35 +842,28 @@ int clrrt_xchg_selftest_path_select(int32_t device, int32_t W, int32_t self, int
         hp[((size_t)r * R + j) * 10 + c] = v;
       }
   XHIP(hipSetDevice(device));
-  char *dp = nullptr, *dd = nullptr;
-  clrrt_node* dn = nullptr;
-  auto run = [&]() -> int {
-    const size_t part = (size_t)R * PROW;
-    XHIP(hipMalloc((void**)&dp, std::max<size_t>(part * W, 16)));
-    XHIP(hipMalloc((void**)&dd, std::max<size_t>(part, 16)));
-    XHIP(hipMalloc((void**)&dn, std::max<size_t>(sizeof(clrrt_node) * n, 16)));
-    if (R > 0) {
-      XHIP(hipMemcpy(dp, hp.data(), part * W, hipMemcpyHostToDevice));
-      XHIP(hipMemcpy(dd, hp.data() + (size_t)self * R * 10, part, hipMemcpyHostToDevice));  // its own pattern
-      XHIP(hipMemcpy(dn, hn.data(), sizeof(clrrt_node) * n, hipMemcpyHostToDevice));
-    }
-    PathSelectArgs a{};
-    a.parts = (const uint4*)dp;
-    a.dst = (uint4*)dd;
-    a.nodes = dn;
-    a.rows = R;
-    a.n = n;
-    a.W = W;
-    a.self = self;
-    XHIP(launch_path_select(nullptr, a));
-    XHIP(hipDeviceSynchronize());
-    if (R > 0) XHIP(hipMemcpy(out_rows, dd, part, hipMemcpyDeviceToHost));
-    return CLRRT_OK;
-  };
-  const int rc = run();
-  for (void* p : {(void*)dp, (void*)dd, (void*)dn})
-    if (p) (void)hipFree(p);
-  if (rc != CLRRT_OK) return rc;
+  const size_t part = (size_t)R * PROW;
+  Scratch<char> dp, dd;
+  Scratch<clrrt_node> dn;
+  XHIP(dp.alloc(std::max<size_t>(part * W, 16)));
+  XHIP(dd.alloc(std::max<size_t>(part, 16)));
+  XHIP(dn.alloc(n));
+  if (R > 0) {
+    XHIP(hipMemcpy(dp, hp.data(), part * W, hipMemcpyHostToDevice));
+    XHIP(hipMemcpy(dd, hp.data() + (size_t)self * R * 10, part, hipMemcpyHostToDevice));  // its own pattern
+    XHIP(hipMemcpy(dn, hn.data(), sizeof(clrrt_node) * n, hipMemcpyHostToDevice));
+  }
+  PathSelectArgs a{};
+  a.parts = (const uint4*)dp.p;
+  a.dst = (uint4*)dd.p;
+  a.nodes = dn;
+  a.rows = R;
+  a.n = n;
+  a.W = W;
+  a.self = self;
+  XHIP(launch_path_select(nullptr, a));
+  XHIP(hipDeviceSynchronize());
+  if (R > 0) XHIP(hipMemcpy(out_rows, dd, part, hipMemcpyDeviceToHost));
   *out_moved = moved;
   return CLRRT_OK;
 }

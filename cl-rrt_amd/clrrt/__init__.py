@@ -96,6 +96,9 @@ _SIGS = {
     "clrrt_search_work": (C.c_int, [C.c_void_p, P(C.c_int64)]),
     "clrrt_search_work_ex": (C.c_int, [C.c_void_p, P(C.c_int64)]),
     "clrrt_walk_audit": (C.c_int, [C.c_void_p, P(abi.Sample), C.c_int32, P(C.c_int32)]),
+    "clrrt_debug_walk_index": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, P(C.c_double)] +
+                               [C.c_void_p] * 9),
+    "clrrt_selftest_walk": (C.c_int, [C.c_void_p, C.c_int32, P(C.c_float), C.c_int32, P(C.c_float)]),
     "clrrt_round_sizes": (C.c_int, [C.c_void_p, P(C.c_int64), C.c_int64, P(C.c_int64)]),
     "clrrt_tree_truncate": (C.c_int, [C.c_void_p, C.c_int64]),
     "clrrt_iteration_log": (C.c_int, [C.c_void_p, C.c_int32]),
@@ -658,6 +661,44 @@ class Planner:
         arr = (abi.Sample * n)(*samples)
         out = np.zeros((n, 20), dtype=np.int32)
         self._chk(self.L.clrrt_walk_audit(self.h, arr, n, out.ctypes.data_as(P(C.c_int32))), "walk_audit")
+        return out
+
+    # a tile / super-tile record of the walk index (WalkTile, clrrt_internal.hpp)
+    WALK_TILE_DTYPE = np.dtype([(f, np.float32) for f in ("pcx", "pcy", "pr", "rcx", "rcy", "rr", "thx", "thy", "thh",
+                                                         "apx", "apy", "aph", "cemin", "aopt")] +
+                               [("nonfinite", np.int32), ("eroot", np.float32)])
+    WALK_FN_IN = {0: 3, 1: 3, 2: 21, 3: 2, 4: 2}
+    WALK_FN_OUT = {0: 2, 1: 2, 2: 2, 3: 2, 4: 3}
+
+    def walk_index(self, first=0, count=None, fused=False):
+        """clrrt_debug_walk_index (test hook): the walk index of nodes [first, first + count) as the whole-tree /
+        range builder (fused False) or the appended-node builder (fused True) makes it.  A dict of numpy arrays: P, Q
+        (Npad, 4), CE, ID, HEAD (Npad,), trun (tiles, 2), tiles and supers (structured, WALK_TILE_DTYPE), roster
+        (66,), and the header values npad, ntiles, nsup, ox, oy, delta, slack, R (2,)."""
+        if count is None:
+            count = self.size()[0] - first
+        npad = (max(int(count), 0) + 1023) // 1024 * 1024
+        nt, ns = npad // 32, npad // 1024
+        out = {"P": np.zeros((npad, 4), np.float32), "Q": np.zeros((npad, 4), np.float32),
+               "CE": np.zeros(npad, np.float32), "ID": np.zeros(npad, np.int32), "HEAD": np.zeros(npad, np.int32),
+               "trun": np.zeros((nt, 2), np.int32), "tiles": np.zeros(nt, self.WALK_TILE_DTYPE),
+               "supers": np.zeros(ns, self.WALK_TILE_DTYPE), "roster": np.zeros(66, np.int32)}
+        hdr = (C.c_double * 9)()
+        ptrs = [out[k].ctypes.data for k in ("P", "Q", "CE", "ID", "HEAD", "trun", "tiles", "supers", "roster")]
+        self._chk(self.L.clrrt_debug_walk_index(self.h, int(first), int(count), 1 if fused else 0, hdr, *ptrs),
+                  "walk_index")
+        assert (int(hdr[0]), int(hdr[1]), int(hdr[2])) == (npad, nt, ns)
+        out.update(npad=npad, ntiles=nt, nsup=ns, ox=hdr[3], oy=hdr[4], delta=hdr[5], slack=hdr[6],
+                   R=np.array([hdr[7], hdr[8]]), first=int(first), count=int(count), fused=bool(fused))
+        return out
+
+    def selftest_walk(self, fn, cases):
+        """clrrt_selftest_walk (test hook): the walk's bound functions on the device, cases [n, WALK_FN_IN[fn]]
+        float32 -> [n, WALK_FN_OUT[fn]] float32 (fn 2 takes a tile record's 16 raw words first)."""
+        cases = np.ascontiguousarray(cases, dtype=np.float32).reshape(-1, self.WALK_FN_IN[fn])
+        out = np.zeros((cases.shape[0], self.WALK_FN_OUT[fn]), dtype=np.float32)
+        self._chk(self.L.clrrt_selftest_walk(self.h, fn, cases.ctypes.data_as(P(C.c_float)), cases.shape[0],
+                                             out.ctypes.data_as(P(C.c_float))), "selftest_walk")
         return out
 
     def search_work_ex(self):

@@ -3800,4 +3800,80 @@ int clrrt_walk_audit(clrrt_ctx* c, const clrrt_sample* samples, int32_t n, int32
   return CLRRT_OK;
 }
 
+int clrrt_debug_walk_index(clrrt_ctx* c, int64_t first, int64_t count, int32_t fused, double hdr[9], float* P,
+                           float* Q, float* CE, int32_t* ID, int32_t* HEAD, int32_t* trun, void* tiles, void* supers,
+                           int32_t* roster) {
+  if (!c || !hdr) return CLRRT_EINVAL;
+  if (first < 0 || count <= 0 || first > c->n_nodes || count > c->n_nodes - first)
+    return fail(c, CLRRT_EINVAL, "debug_walk_index: node range outside the tree");
+  pf_reset(c);
+  HIPC(c, hipSetDevice(c->device));
+  const NnSetup su = nn_setup(c);
+  const bool whole = !fused && first == 0 && count == c->n_nodes;
+  if (!su.region_ok || c->n_nodes < c->nnw_min_nodes || (!fused && !whole && count < c->nnw_min_nodes))
+    return fail(c, CLRRT_ESTATE, "the walk does not serve this tree (too small or no region)");
+  int rc = CLRRT_OK;
+  WalkBufs* w = nullptr;
+  if (fused) {
+    if ((rc = alloc_walk_delta(c)) != CLRRT_OK) return rc;
+    w = &c->nnw_d;
+    if (count > w->cap_nodes) return fail(c, CLRRT_ECAPACITY, "debug_walk_index: range beyond the appended-node set");
+    HIPC(c, launch_nn_delta_index(c->stream, c->nn, (int)first, (int)count, su.fr, su.x0, su.y0, su.x1, su.y1, *w));
+  } else if (whole) {
+    if ((rc = ensure_walk(c)) != CLRRT_OK) return rc;
+    w = &c->nnw;
+    c->nnw_built.n = -1;
+    HIPC(c, launch_nn_walk_build(c->stream, c->nn, (int)count, su.fr, su.x0, su.y0, su.x1, su.y1, *w));
+  } else {
+    w = &c->nnw_r;
+    if ((rc = ensure_walk_set(c, *w)) != CLRRT_OK) return rc;
+    c->nnr_built.n = -1;
+    HIPC(c, launch_nn_walk_build(c->stream, c->nn, (int)count, su.fr, su.x0, su.y0, su.x1, su.y1, *w, nullptr,
+                                 (int)first));
+  }
+  const char* const pre = "debug_walk_index: ";
+  const size_t nt = (size_t)walk_tile_count(count), ns = (size_t)walk_super_count(count), np = nt * 32;
+  NnRec r0;
+  HIPP(c, pre, hipMemcpyAsync(&r0, c->nn, sizeof(NnRec), hipMemcpyDeviceToHost, c->stream));
+  if (P) HIPP(c, pre, hipMemcpyAsync(P, w->P, sizeof(float4) * np, hipMemcpyDeviceToHost, c->stream));
+  if (Q) HIPP(c, pre, hipMemcpyAsync(Q, w->Q, sizeof(float4) * np, hipMemcpyDeviceToHost, c->stream));
+  if (CE) HIPP(c, pre, hipMemcpyAsync(CE, w->CE, sizeof(float) * np, hipMemcpyDeviceToHost, c->stream));
+  if (ID) HIPP(c, pre, hipMemcpyAsync(ID, w->ID, sizeof(int) * np, hipMemcpyDeviceToHost, c->stream));
+  if (HEAD) HIPP(c, pre, hipMemcpyAsync(HEAD, w->HEAD, sizeof(int) * np, hipMemcpyDeviceToHost, c->stream));
+  if (trun) HIPP(c, pre, hipMemcpyAsync(trun, w->trun, sizeof(int2) * nt, hipMemcpyDeviceToHost, c->stream));
+  if (tiles) HIPP(c, pre, hipMemcpyAsync(tiles, w->tiles, sizeof(WalkTile) * nt, hipMemcpyDeviceToHost, c->stream));
+  if (supers) HIPP(c, pre, hipMemcpyAsync(supers, w->supers, sizeof(WalkTile) * ns, hipMemcpyDeviceToHost, c->stream));
+  if (roster) {
+    memset(roster, 0, sizeof(int32_t) * 66);
+    roster[1] = -1;
+    if (!fused && w->roster)
+      HIPP(c, pre, hipMemcpyAsync(roster, w->roster, sizeof(int32_t) * 66, hipMemcpyDeviceToHost, c->stream));
+  }
+  HIPP(c, pre, hipStreamSynchronize(c->stream));
+  hdr[0] = (double)np; hdr[1] = (double)nt; hdr[2] = (double)ns;
+  hdr[3] = su.fr.ox; hdr[4] = su.fr.oy; hdr[5] = (double)su.fr.delta;
+  hdr[6] = (double)su.fr.delta;  // the builders' slack is the frame's delta
+  hdr[7] = (double)(float)(r0.x - su.fr.ox); hdr[8] = (double)(float)(r0.y - su.fr.oy);  // k_walk_tiles' R
+  return CLRRT_OK;
+}
+
+int clrrt_selftest_walk(clrrt_ctx* c, int32_t fn, const float* in, int32_t n, float* out) {
+  static const int kin[5] = {3, 3, 21, 2, 2};
+  static const int kout[5] = {2, 2, 2, 2, 3};
+  if (!c || n < 0 || (n > 0 && (!in || !out)) || fn < 0 || fn > 4) return CLRRT_EINVAL;
+  HIPC(c, hipSetDevice(c->device));
+  if (n == 0) return CLRRT_OK;
+  const size_t nin = (size_t)kin[fn] * n, nout = (size_t)kout[fn] * n;
+  const char* const pre = "selftest_walk: ";
+  Scratch<float> din, dout;
+  HIPP(c, pre, din.alloc(nin));
+  HIPP(c, pre, dout.alloc(nout));
+  HIPP(c, pre, hipMemcpyAsync(din, in, sizeof(float) * nin, hipMemcpyHostToDevice, c->stream));
+  HIPP(c, pre, hipMemsetAsync(dout, 0, sizeof(float) * nout, c->stream));
+  HIPP(c, pre, launch_selftest_walk(c->stream, fn, din, n, dout));
+  HIPP(c, pre, hipMemcpyAsync(out, dout, sizeof(float) * nout, hipMemcpyDeviceToHost, c->stream));
+  HIPP(c, pre, hipStreamSynchronize(c->stream));
+  return CLRRT_OK;
+}
+
 }  // extern "C"

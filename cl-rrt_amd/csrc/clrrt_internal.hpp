@@ -194,7 +194,7 @@ struct NnFrame {
   float delta;
   int debug;  // diagnostics only (results change!): 1 = skip the exact pass
 };
-// Bounds of a tile (64 place-ordered records) or super-tile (1024) of the walk search
+// Bounds of a tile (32 place-ordered records, WALK_TILE) or super-tile (1024) of the walk search
 // (clrrt_nnwalk.hip), frame coordinates.
 struct WalkTile {
   float pcx, pcy, pr;  // disc holding the node positions (pr < 0: no records)
@@ -298,6 +298,11 @@ int64_t walk_delta_cap(int64_t max_nodes, int64_t max_batch);
 hipError_t launch_nn_delta_walk(hipStream_t st, const clrrt_sample* S, int B, const NnRec* nodes, int first, int count,
                                 const DevParams& p, const NnFrame& fr, double x0, double y0, double x1, double y1,
                                 WalkBufs& w, float* pk, int* pi, float* seed, unsigned long long* stats);
+// launch_nn_delta_walk's index alone: keys, sort and the fused index kernel (k_walk_range_index) into w.
+hipError_t launch_nn_delta_index(hipStream_t st, const NnRec* nodes, int first, int count, const NnFrame& fr, double x0,
+                                 double y0, double x1, double y1, WalkBufs& w);
+// Test hook (clrrt_selftest_walk): the walk's bound functions, one case per lane; formats in clrrt.h.
+hipError_t launch_selftest_walk(hipStream_t st, int fn, const float* in, int n, float* out);
 // Option nn_delta_verify: the brute force's chunk lists (pk / pi, ids relative to id0) against the walk's lists (wk /
 // wi) of the same search; out[0] += samples compared, out[1] += samples whose NN_K (key bits, id) pairs differ.
 hipError_t launch_nn_delta_compare(hipStream_t st, int B, int nchunks, int id0, const float* pk, const int* pi,

@@ -669,6 +669,49 @@ __device__ __forceinline__ int lc_le(float v) {  // the largest code c with lc_d
   return v == __builtin_inff() ? 255 : lc_enc(v);
 }
 
+// The bound functions above as the search compiles them, one case per lane (test hook, clrrt_selftest_walk: the
+// bounds against the exact keys of clrrt_selftest_units, tests/test_walk_index.py).  Formats: clrrt.h.
+__global__ void k_selftest_walk(int fn, const float* __restrict__ in, int n, float* __restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  switch (fn) {
+    case 0:
+    case 1: {
+      const float* a = in + 3 * (int64_t)i;
+      float lo, hi;
+      if (fn == 0) walk_key_range<false>(a[0], a[1], a[2], lo, hi);
+      else walk_key_range<true>(a[0], a[1], a[2], lo, hi);
+      out[2 * (int64_t)i] = lo;
+      out[2 * (int64_t)i + 1] = hi;
+    } break;
+    case 2: {  // the tile's 16 words as downloaded (clrrt_debug_walk_index), then rsx, rsy, ex, flen, dsR
+      const float* a = in + 21 * (int64_t)i;
+      WalkTile w;
+      memcpy(&w, a, sizeof(WalkTile));
+      out[2 * (int64_t)i] = walk_lb(w, a[16], a[17], a[18] != 0.f, a[19], a[20]);
+      out[2 * (int64_t)i + 1] = walk_lb_dist(w, a[16], a[17], a[18] != 0.f, a[20]);
+    } break;
+    case 3: {  // (y, x)
+      const float* a = in + 2 * (int64_t)i;
+      out[2 * (int64_t)i] = acos_apx(a[1]);
+      out[2 * (int64_t)i + 1] = atan2_apx(a[0], a[1]);
+    } break;
+    case 4: {  // (b, c): codes travel as float values (0 .. 255 are exact)
+      const float* a = in + 2 * (int64_t)i;
+      const int c = (int)fminf(fmaxf(a[1], 0.f), 255.f);
+      out[3 * (int64_t)i] = (float)lc_enc(a[0]);
+      out[3 * (int64_t)i + 1] = (float)lc_le(a[0]);
+      out[3 * (int64_t)i + 2] = lc_dec(c);
+    } break;
+  }
+}
+hipError_t launch_selftest_walk(hipStream_t st, int fn, const float* in, int n, float* out) {
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_selftest_walk, dim3((n + 255) / 256), dim3(256), 0, st, fn, in, n, out);
+  LAUNCH_CHECK3();
+  return hipSuccess;
+}
+
 // One wave per sample.  LDS per super-tile: s_lb = a lower bound (one log-coded byte, rounded down) of the keys in
 // its tiles not yet visited.  Pass k visits the tiles whose bound lies in (T_{k-1}, min(T_k, kth)]
 // (T_k grows geometrically from the smallest bound; a tile's bound is max(tile bound, super-tile
@@ -2011,13 +2054,14 @@ int64_t walk_delta_cap(int64_t max_nodes, int64_t max_batch) {
   return std::min<int64_t>(max_nodes, 6 * max_batch + 1024);
 }
 
-hipError_t launch_nn_delta_walk(hipStream_t st, const clrrt_sample* S, int B, const NnRec* nodes, int first, int count,
-                                const DevParams& p, const NnFrame& fr, double x0, double y0, double x1, double y1,
-                                WalkBufs& w, float* pk, int* pi, float* seed, unsigned long long* stats) {
-  if (count <= 0 || B <= 0) return hipSuccess;
+// launch_nn_delta_walk's index of nodes [first, first + count) in w: keys, sort and the fused index kernel (also what
+// clrrt_debug_walk_index downloads with fused = 1).
+hipError_t launch_nn_delta_index(hipStream_t st, const NnRec* nodes, int first, int count, const NnFrame& fr, double x0,
+                                 double y0, double x1, double y1, WalkBufs& w) {
+  if (count <= 0) return hipSuccess;
   if (count > w.cap_nodes) return hipErrorInvalidValue;
   const int Npad = (count + WALK_TILE * WALK_SUPER - 1) / (WALK_TILE * WALK_SUPER) * (WALK_TILE * WALK_SUPER);
-  const int ntiles = Npad / WALK_TILE, nsup = ntiles / WALK_SUPER;
+  const int nsup = Npad / (WALK_TILE * WALK_SUPER);
   // the keys of launch_nn_walk_build (the search's frame; the order only sets how tight the bounds are)
   const int kind = w.index_kind;
   const double hrho = 4.77 * (w.hscale_pct > 0 ? w.hscale_pct : 100) * 0.01;
@@ -2033,6 +2077,17 @@ hipError_t launch_nn_delta_walk(hipStream_t st, const clrrt_sample* S, int B, co
   hipLaunchKernelGGL(k_walk_range_index, dim3(nsup), dim3(WALK_TILE * WALK_SUPER), 0, st, nodes, count,
                      (const int*)w.sids, fr.ox, fr.oy, fr.delta, w.P, w.Q, w.CE, w.ID, w.HEAD, w.trun, w.tiles, w.supers);
   LAUNCH_CHECK3();
+  return hipSuccess;
+}
+
+hipError_t launch_nn_delta_walk(hipStream_t st, const clrrt_sample* S, int B, const NnRec* nodes, int first, int count,
+                                const DevParams& p, const NnFrame& fr, double x0, double y0, double x1, double y1,
+                                WalkBufs& w, float* pk, int* pi, float* seed, unsigned long long* stats) {
+  if (count <= 0 || B <= 0) return hipSuccess;
+  hipError_t e = launch_nn_delta_index(st, nodes, first, count, fr, x0, y0, x1, y1, w);
+  if (e != hipSuccess) return e;
+  const int Npad = (count + WALK_TILE * WALK_SUPER - 1) / (WALK_TILE * WALK_SUPER) * (WALK_TILE * WALK_SUPER);
+  const int ntiles = Npad / WALK_TILE, nsup = ntiles / WALK_SUPER;
   hipLaunchKernelGGL(k_walk_delta, dim3(B), dim3(64), 2 * sizeof(float) * (size_t)nsup, st, S, B, nodes, w.P, w.Q, w.CE,
                      w.ID, w.HEAD, w.trun, w.tiles, ntiles, w.supers, nsup, p, fr, (const float*)seed, stats, pk, pi);
   LAUNCH_CHECK3();

@@ -661,6 +661,29 @@ int clrrt_search_work_ex(clrrt_ctx* ctx, int64_t out[8]);
  * those inside one run of equal key inputs, 17 records of the tiles of q = 0 in such a run; 18, 19 reserved.  out
  * holds 20 values per sample. */
 int clrrt_walk_audit(clrrt_ctx* ctx, const clrrt_sample* samples, int32_t n, int32_t* out);
+/* Test hook: the walk search's index (clrrt_nnwalk.hip) of nodes [first, first + count) of the current tree, built
+ * and copied out.  fused = 0: the builder of the searches over kept indexes -- the whole-tree index when first = 0 and
+ * count = the tree size (as clrrt_walk_audit builds it), else the range index of clrrt_nn_range; fused = 1: the
+ * one-launch builder of the appended-node walk (lag-2 rounds), whose runs of equal records are cut at super-tile
+ * boundaries and which makes no roster.  With Npad = count rounded up to a multiple of 1024, the outputs (each may be
+ * NULL) are P, Q [Npad][4] floats (x, y, c, s), (ref.back() x, y, cos, sin ang_par) relative to the frame origin, CE
+ * [Npad] costE, ID [Npad] node ids in place order (-1: padding), HEAD [Npad] run heads (bit 30: the record's key
+ * inputs equal node 0's), trun [Npad / 32][2], tiles [Npad / 32] and supers [Npad / 1024] records of 16 words (floats
+ * pcx, pcy, pr, rcx, rcy, rr, thx, thy, thh, apx, apy, aph, cemin, aopt, int32 nonfinite, float eroot), roster [66]
+ * (entries, X, ids; 0, -1 where the builder makes none).  hdr: Npad, tiles, super-tiles, frame origin x, y, the
+ * frame's delta, the slack the builder was given, and the bounds' fixed point R (x, y) as the builder forms it.
+ * CLRRT_ESTATE where no walk serves the tree or the range (options nn_walk_min, no sample region), CLRRT_ECAPACITY
+ * where the range exceeds the builder's buffer set (fused = 1: the appended-node set).  Kept indexes are invalidated. */
+int clrrt_debug_walk_index(clrrt_ctx* ctx, int64_t first, int64_t count, int32_t fused, double hdr[9], float* P,
+                           float* Q, float* CE, int32_t* ID, int32_t* HEAD, int32_t* trun, void* tiles, void* supers,
+                           int32_t* roster);
+/* Test hook: the walk search's bound functions as its kernels compile them, one case per lane (floats), in -> out:
+ *   fn 0 / 1  tx, ty, pos_err -> lo, hi of walk_key_range without / with the inside-circle bracket  [3 -> 2]
+ *   fn 2      a tile record's 16 words (clrrt_debug_walk_index), rsx, rsy, explore (0 / 1), flen, dsR
+ *             -> walk_lb, walk_lb_dist  [21 -> 2]
+ *   fn 3      y, x -> acos_apx(x), atan2_apx(y, x)  [2 -> 2]
+ *   fn 4      b, c -> lc_enc(b), lc_le(b), lc_dec(c) (codes as float values)  [2 -> 3] */
+int clrrt_selftest_walk(clrrt_ctx* ctx, int32_t fn, const float* in, int32_t n, float* out);
 /* Engine extension: the tree size after each commit of the last clrrt_expand -- its rounds in order, then the commit
  * of the deferred samples still pending at its end (defer_steps), when there were any -- into out[0 .. min(n, cap));
  * *n = the count.  With deferred samples, round r's samples are evaluated against the tree of out[r - 1] nodes (the

@@ -9,6 +9,10 @@ relies on, with the margins it uses:
   * acos_apx (Abramowitz & Stegun 4.4.45) within 1e-4 rad of acos on [-1, 1];
   * atan2_apx (A&S 4.4.49) within 1e-6 rad of atan2, and walk_key_range (the stage-1 key bounds of
     the walk's drains) below / above the key of every offset within pos_err of its own.
+
+These are numpy restatements: they check the formulas, not the compiled kernel.  The kernel's own acos_apx, atan2_apx
+and walk_key_range (hardware rcp / sqrt, the constants as compiled) are checked on the device against the float key the
+searches compute by tests/test_walk_index.py (clrrt_selftest_walk).
 """
 import numpy as np
 import pytest

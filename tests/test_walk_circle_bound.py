@@ -12,6 +12,10 @@ tests/test_nnwalk_bounds.py) of member records on the disc's rim and at the arc'
 GPU: a clustered synthetic tree (whole tiles with small discs and arcs) with samples abeam of the clusters, on the
 circle boundary, ahead and behind: the walk's lists equal the brute force's, and pipelined rounds grow the tree of
 unpipelined brute-force rounds.
+
+The CPU part checks the formula as restated here, not the compiled kernel: walk_lb itself, given the tile records the
+index builders make, is checked on the device against the exact keys of every tile member by tests/test_walk_index.py
+(clrrt_selftest_walk, clrrt_debug_walk_index).
 """
 import numpy as np
 import pytest

@@ -101,6 +101,7 @@ _SIGS = {
     "clrrt_selftest_walk": (C.c_int, [C.c_void_p, C.c_int32, P(C.c_float), C.c_int32, P(C.c_float)]),
     "clrrt_round_sizes": (C.c_int, [C.c_void_p, P(C.c_int64), C.c_int64, P(C.c_int64)]),
     "clrrt_tree_truncate": (C.c_int, [C.c_void_p, C.c_int64]),
+    "clrrt_tree_rebase": (C.c_int, [C.c_void_p, C.c_int64, P(C.c_double), C.c_double, P(abi.RebaseInfo)]),
     "clrrt_iteration_log": (C.c_int, [C.c_void_p, C.c_int32]),
     "clrrt_exact_stats": (C.c_int, [C.c_void_p, P(C.c_int64)]),
     "clrrt_iteration_records": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, P(abi.Iteration), P(C.c_int64)]),
@@ -371,6 +372,16 @@ class Planner:
         self._chk(self.L.clrrt_tree_init_from_path(self.h, cs.ctypes.data_as(P(C.c_double)), C.byref(oc)),
                   "tree_init_from_path")
         return oc.value
+
+    def tree_rebase(self, root_id, pose, t_shift=0.0):
+        """clrrt_tree_rebase: the tree becomes the subtree of node root_id in the car frame `pose` (x, y, heading in
+        the tree's present frame), times shifted by t_shift, re-checked against the current scene, compacted and
+        re-costed on the device.  Returns the clrrt_rebase_info fields as a dict (outcome: abi.REBASE_*)."""
+        pose = np.ascontiguousarray(np.asarray(pose, dtype=np.float64)[:3])
+        info = abi.RebaseInfo()
+        self._chk(self.L.clrrt_tree_rebase(self.h, int(root_id), pose.ctypes.data_as(P(C.c_double)), float(t_shift),
+                                           C.byref(info)), "tree_rebase")
+        return {k: getattr(info, k) for k, _ in abi.RebaseInfo._fields_}
 
     def path_mpc_message(self, filtered=True):
         """(P, 8) array x, y, theta, delta, v, a, a_cmd, d_cmd of the committed path's MPC message."""

@@ -66,6 +66,15 @@ class ClearanceInfo(C.Structure):  # clrrt_clearance_info_t
                 ("bake_ms", C.c_double)]
 
 
+REBASE_KEPT, REBASE_ROOT_COLLIDES = 0, 1  # CLRRT_REBASE_*
+
+
+class RebaseInfo(C.Structure):  # clrrt_rebase_info
+    _fields_ = [("outcome", C.c_int32), ("depth", C.c_int32), ("nodes_before", C.c_int64),
+                ("nodes_subtree", C.c_int64), ("nodes_collided", C.c_int64), ("nodes_kept", C.c_int64),
+                ("rows_before", C.c_int64), ("rows_kept", C.c_int64), ("device_ms", C.c_double)]
+
+
 class Node(C.Structure):
     _fields_ = [
         ("state", C.c_double * 10), ("ref_front", C.c_double * 2), ("ref_back", C.c_double * 2),
@@ -135,6 +144,7 @@ def _check_sizes():
     assert C.sizeof(ExchangeIO) == 128, C.sizeof(ExchangeIO)
     assert C.sizeof(Occupancy) == 40 and C.sizeof(OccupancyInfo) == 48
     assert C.sizeof(ClearanceInfo) == 32
+    assert C.sizeof(RebaseInfo) == 64
 
 
 _check_sizes()

@@ -66,18 +66,51 @@ class PlannerBackend:
     """The five planMotion steps on the HIP planner (clrrt.Planner).  complete_path: with a sharded planner, the
     collective that completes the committed path's rows across the ranks, called in every query between path_commit
     and path_transform with the planner (clrrt.dist.NativeExchange.path_rows, or
-    lambda pl: clrrt.dist.fetch_path_rows(pl, rank)); its result (rows moved) is kept in rows_fetched."""
+    lambda pl: clrrt.dist.fetch_path_rows(pl, rank)); its result (rows moved) is kept in rows_fetched.
 
-    def __init__(self, planner, make_params, complete_path=None):
+    carry_tree (engine extension, default False: nothing changes): the tree is kept between queries instead of being
+    cut down to the committed path.  begin_query then picks as new root the tree id of the first committed-path node
+    that initializeTree's filter would keep (its last row has x >= 0 in the new car frame), calls
+    Planner.tree_rebase with the new car pose expressed in the previous car frame and t_shift = that node's state[6],
+    and falls back to tree_init_from_path when there is no such node or the root's row collides.  The committed path is
+    transformed either way.  last_rebase: the rebase info of the last query that carried its tree (else None).  Not
+    with a sharded planner."""
+
+    def __init__(self, planner, make_params, complete_path=None, carry_tree=False):
+        if carry_tree and complete_path is not None:
+            raise ValueError("carry_tree is not supported with a sharded planner")
         self.pl = planner
         self.make_params = make_params
         self.complete_path = complete_path
         self.rows_fetched = 0
+        self.carry_tree = carry_tree
+        self.last_rebase = None
+        self._carry = None  # (previous pose, path ids, last world row per path node, state[6] per path node)
+
+    def _carry_root(self, pose):
+        """(tree id, t_shift) of the first committed-path node whose last row has x >= 0 in the car frame of `pose`
+        (the nodes initializeTree keeps, rrtplanner.cpp:51-57: NaN is kept), or None."""
+        _, ids, last_rows, times = self._carry
+        for i, tree_id in enumerate(ids):
+            x, _ = world_to_car_pose(last_rows[i, 0], last_rows[i, 1], pose)
+            if not x < 0:
+                return tree_id, times[i]
+        return None
 
     def begin_query(self, pose, goal_car, obs_car):
         self.pl.set_params(self.make_params(pose[4], goal_car))
         self.pl.set_obstacles(obs_car)
         self.pl.path_transform(False, pose)
+        self.last_rebase = None
+        if self.carry_tree and self._carry is not None:
+            root = self._carry_root(pose)
+            if root is not None:
+                prev = self._carry[0]
+                px, py = world_to_car_pose(pose[0], pose[1], prev)
+                info = self.pl.tree_rebase(root[0], [px, py, pose[2] - prev[2]], root[1])
+                if info["outcome"] == abi.REBASE_KEPT:
+                    self.last_rebase = info
+                    return abi.REINIT_KEPT
         return self.pl.tree_init_from_path([0.0, 0.0, 0.0, pose[3], pose[4], pose[5]])
 
     def end_query(self, pose):
@@ -86,7 +119,10 @@ class PlannerBackend:
         if self.complete_path is not None:
             self.rows_fetched = self.complete_path(self.pl)
         self.pl.path_transform(True, pose)
-        _, rows = self.pl.path_download()
+        nodes, rows = self.pl.path_download()
+        if self.carry_tree:
+            last = np.array([rows[nd.row_offset + nd.nrows - 1] for nd in nodes]).reshape(-1, 10)
+            self._carry = (np.array(pose, dtype=np.float64), list(ids), last, [nd.state[6] for nd in nodes])
         return ids, rows
 
 

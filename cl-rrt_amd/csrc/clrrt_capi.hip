@@ -100,6 +100,8 @@ struct clrrt_ctx {
   NnRec* nn = nullptr;
   double* arena = nullptr;
   int64_t n_nodes = 0, n_rows = 0;
+  bool tree_rowless = false;  // the tree came from clrrt_tree_load: its first nodes have no rows in the arena
+  int64_t rebase_window_rows = 786432;  // option "rebase_window_rows": clrrt_tree_rebase's move window (60 MiB)
   // obstacles
   BakedObs* obs = nullptr;
   int n_obs = 0;
@@ -416,8 +418,9 @@ struct clrrt_ctx {
   // 3 the walk searches alone (launch_nn_walk_search: sample order, k_walk_search, split + merge; within class 0),
   // 4 the main stream's wait for a round's lists (the side streams' walk + merge running past the work queued
   // before it: the search's share of the round's critical path), 5 sharded exchanges (the stream span from the
-  // records' copy to the gathered records' availability: the collective on the critical path)
-  static constexpr int kKtClasses = 6;
+  // records' copy to the gathered records' availability: the collective on the critical path), 6 clrrt_tree_rebase's
+  // check kernel (k_rebase_check alone: its bandwidth basis is rows x 80 B)
+  static constexpr int kKtClasses = 7;
   double kt_ms[kKtClasses] = {};
   int64_t kt_n[kKtClasses] = {};
   std::vector<hipEvent_t> ev_pool;
@@ -1179,6 +1182,7 @@ int clrrt_tree_init(clrrt_ctx* c, const double root_state[10]) {
   HIPP(c, "tree_init: ", hipStreamSynchronize(c->stream));
   c->n_nodes = 1;
   c->n_rows = 1;
+  c->tree_rowless = false;
   bbox_reset(c);
   if (std::isfinite(root_state[0]) && std::isfinite(root_state[1]))
     bbox_add(c, root_state[0], root_state[1], root_state[0], root_state[1]);
@@ -1200,6 +1204,7 @@ int clrrt_tree_load(clrrt_ctx* c, const clrrt_node* nodes, int64_t n) {
   }
   c->n_nodes = n;
   c->n_rows = 0;
+  c->tree_rowless = true;
   bbox_reset(c);
   for (int64_t i = 0; i < n; i++)
     if (std::isfinite(nodes[i].state[0]) && std::isfinite(nodes[i].state[1]))
@@ -1220,6 +1225,175 @@ int clrrt_tree_truncate(clrrt_ctx* c, int64_t n) {
   c->n_nodes = n;
   if (h.row_offset >= 0 && h.row_offset <= c->n_rows) c->n_rows = h.row_offset;  // rows are appended in node order
   return CLRRT_OK;  // (the tree's box stays a superset: a valid search frame)
+}
+
+int clrrt_tree_rebase(clrrt_ctx* c, int64_t root_id, const double pose[3], double t_shift, clrrt_rebase_info* out) {
+  if (!c || !pose) return CLRRT_EINVAL;
+  if (root_id < 0 || root_id >= c->n_nodes) return fail(c, CLRRT_EINVAL, "tree_rebase: root_id outside the tree");
+  if (!(std::isfinite(pose[0]) && std::isfinite(pose[1]) && std::isfinite(pose[2]) && std::isfinite(t_shift)))
+    return fail(c, CLRRT_EINVAL, "tree_rebase: non-finite pose or t_shift");
+  if (c->sh.world > 1) return fail(c, CLRRT_ESTATE, "tree_rebase: not with a sharded tree (clrrt_set_shards world > 1)");
+  if (c->tree_rowless || c->n_rows <= 0)
+    return fail(c, CLRRT_ESTATE, "tree_rebase: the tree has no rows (clrrt_tree_load)");
+  HIPC(c, hipSetDevice(c->device));
+  int rc = flush_replays(c);  // deferred rows of committed nodes land first
+  if (rc != CLRRT_OK) return rc;
+  const char* const pre = "tree_rebase: ";
+  const int n = (int)c->n_nodes, root = (int)root_id;
+  const int64_t n_rows = c->n_rows;
+  const int ts = c->dp.bend ? 2 : 1;
+  hipStream_t st = c->stream;
+  hipEvent_t ev0 = ev_get(c), ev1 = ev_get(c);
+  if (!ev0 || !ev1) return fail(c, CLRRT_EHIP, "tree_rebase: no event");
+  struct EvBack {  // the events return to the pool on every exit
+    clrrt_ctx* c; hipEvent_t a, b;
+    ~EvBack() { c->ev_pool.push_back(a); c->ev_pool.push_back(b); }
+  } evback{c, ev0, ev1};
+  // per-node scratch (ints: jump, hop, bad double-buffered, row counts, flags, one error word, one moved word), the
+  // scan's buffers and the per-row cost terms (8 or 16 bytes per row of the tree: the one buffer that grows with the
+  // rows; the move's window below does not)
+  Scratch<int> ints;
+  Scratch<int64_t> roff;
+  Scratch<uint64_t> scan;
+  Scratch<unsigned long long> stats;
+  Scratch<double> terms, bbox;
+  Scratch<char> tmp;
+  const size_t tmp_bytes = compact_scan_bytes(n);
+  HIPP(c, pre, ints.alloc(8 * (size_t)n + 2));
+  HIPP(c, pre, roff.alloc(n));
+  HIPP(c, pre, scan.alloc(2 * (size_t)n));
+  HIPP(c, pre, stats.alloc(3));
+  HIPP(c, pre, terms.alloc((size_t)ts * n_rows));
+  HIPP(c, pre, bbox.alloc(4));
+  HIPP(c, pre, tmp.alloc(std::max<size_t>(tmp_bytes, 1)));
+  int* jump[2] = {ints, ints + n};
+  int* hop[2] = {ints + 2 * (size_t)n, ints + 3 * (size_t)n};
+  int* bad[2] = {ints + 4 * (size_t)n, ints + 5 * (size_t)n};
+  int* nrw = ints + 6 * (size_t)n;
+  int* nflag = ints + 7 * (size_t)n;
+  int* err = ints + 8 * (size_t)n;
+  int* moved = err + 1;
+  uint64_t* packed = scan;
+  uint64_t* scanned = scan + n;
+  HIPP(c, pre, hipEventRecord(ev0, st));
+  HIPP(c, pre, hipMemsetAsync(nflag, 0, sizeof(int) * ((size_t)n + 2), st));  // flags, err, moved
+  HIPP(c, pre, hipMemsetAsync(stats, 0, sizeof(unsigned long long) * 3, st));
+  HIPP(c, pre, launch_rebase_prep(st, c->tree, n, n_rows, root, roff, nrw, jump[0], hop[0], err));
+  RebaseCheck ck;
+  memset(&ck, 0, sizeof(ck));
+  ck.a = roll_args(c, 0);
+  ck.a.ctr = nullptr;
+  ck.n = n; ck.root = root; ck.n_rows = n_rows;
+  ck.P0 = pose[0]; ck.P1 = pose[1]; ck.P2 = pose[2]; ck.t_shift = t_shift;
+  ck.roff = roff; ck.nrw = nrw; ck.nflag = nflag; ck.terms = terms; ck.tstride = ts;
+  int h_err = 0;
+  HIPP(c, pre, hipMemcpyAsync(&h_err, err, sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPP(c, pre, hipStreamSynchronize(st));
+  if (h_err != 0)  // (before the check kernel, whose row search relies on the layout)
+    return fail(c, CLRRT_ESTATE, h_err == 1 ? "tree_rebase: a parent does not precede its child"
+                                            : "tree_rebase: node rows are not laid out in node order");
+  {
+    KTimer kt(c, 6);
+    HIPP(c, pre, launch_rebase_check(st, ck));
+  }
+  // closure and depth: passes until one moves nothing
+  int cur = 0, passes = 0;
+  for (bool first = true;; first = false) {
+    int h_moved = 0;
+    HIPP(c, pre, hipMemsetAsync(moved, 0, sizeof(int), st));
+    HIPP(c, pre, launch_rebase_double(st, n, root, jump[cur], hop[cur], first ? nflag : bad[cur], jump[cur ^ 1],
+                                      hop[cur ^ 1], bad[cur ^ 1], moved));
+    HIPP(c, pre, hipMemcpyAsync(&h_moved, moved, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPP(c, pre, hipStreamSynchronize(st));
+    cur ^= 1;
+    passes++;
+    if (!h_moved) break;
+    if (passes > 40) return fail(c, CLRRT_ESTATE, "tree_rebase: the parent chains do not end");
+  }
+  HIPP(c, pre, launch_rebase_mark(st, n, root, jump[cur], hop[cur], bad[cur], nflag, nrw, packed, scanned, stats, tmp,
+                                  tmp_bytes));
+  unsigned long long h_stats[3];
+  uint64_t h_last[2];
+  int h_rootflag = 0;
+  HIPP(c, pre, hipMemcpyAsync(h_stats, stats, sizeof(h_stats), hipMemcpyDeviceToHost, st));
+  HIPP(c, pre, hipMemcpyAsync(&h_last[0], packed + (n - 1), sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  HIPP(c, pre, hipMemcpyAsync(&h_last[1], scanned + (n - 1), sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  HIPP(c, pre, hipMemcpyAsync(&h_rootflag, nflag + root, sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPP(c, pre, hipStreamSynchronize(st));
+  clrrt_rebase_info info;
+  memset(&info, 0, sizeof(info));
+  info.nodes_before = n;
+  info.rows_before = n_rows;
+  info.nodes_subtree = (int64_t)h_stats[0];
+  info.nodes_collided = (int64_t)h_stats[1];
+  float ms = 0.f;
+  if (h_rootflag & 1) {  // nothing has been written
+    info.outcome = CLRRT_REBASE_ROOT_COLLIDES;
+    HIPP(c, pre, hipEventRecord(ev1, st));
+    HIPP(c, pre, hipEventSynchronize(ev1));
+    HIPP(c, pre, hipEventElapsedTime(&ms, ev0, ev1));
+    info.device_ms = ms;
+    if (out) *out = info;
+    return CLRRT_OK;
+  }
+  const uint64_t total = h_last[0] + h_last[1];
+  const int nk = (int)(total & 0xffffffffull);
+  const int64_t rows_kept = (int64_t)(total >> 32);
+  const int depth = (int)h_stats[2];
+  // new headers and costs, in scratch
+  Scratch<clrrt_node> hdr;
+  Scratch<int64_t> offs;
+  Scratch<int> lvl;
+  HIPP(c, pre, hdr.alloc(nk));
+  HIPP(c, pre, offs.alloc(2 * (size_t)nk));
+  HIPP(c, pre, lvl.alloc(nk));
+  const double inf4[4] = {HUGE_VAL, HUGE_VAL, -HUGE_VAL, -HUGE_VAL};
+  HIPP(c, pre, hipMemcpyAsync(bbox, inf4, sizeof(inf4), hipMemcpyHostToDevice, st));
+  RebaseHdr ha;
+  ha.tree = c->tree; ha.n = n; ha.root = root; ha.rank = c->rank;
+  ha.P0 = pose[0]; ha.P1 = pose[1]; ha.P2 = pose[2]; ha.t_shift = t_shift;
+  ha.packed = packed; ha.scanned = scanned; ha.hop = hop[cur]; ha.nflag = nflag;
+  ha.hdr = hdr; ha.src = offs; ha.noff = offs + nk; ha.lvl = lvl; ha.bbox = bbox; ha.err = err;
+  HIPP(c, pre, launch_rebase_headers(st, ha));
+  for (int level = 0; level < depth; level++)
+    HIPP(c, pre, launch_rebase_cost(st, nk, level, lvl, ha.src, terms, ts, c->dp.bend, hdr));
+  double h_box[4];
+  HIPP(c, pre, hipMemcpyAsync(&h_err, err, sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPP(c, pre, hipMemcpyAsync(h_box, bbox, sizeof(h_box), hipMemcpyDeviceToHost, st));
+  HIPP(c, pre, hipStreamSynchronize(st));
+  if (h_err != 0) return fail(c, CLRRT_ESTATE, "tree_rebase: node rows are not laid out in node order");
+  // from here the tree changes: rows window by window, then headers and mirror
+  pf_reset(c);
+  c->rep_n = 0;
+  {
+    Scratch<double> win;
+    const int64_t W = std::min<int64_t>(c->rebase_window_rows, rows_kept);
+    HIPP(c, pre, win.alloc(10 * (size_t)W));
+    RebaseMove mv;
+    mv.noff = ha.noff; mv.src = ha.src; mv.nk = nk;
+    mv.P0 = pose[0]; mv.P1 = pose[1]; mv.P2 = pose[2]; mv.t_shift = t_shift;
+    mv.arena = c->arena; mv.win = win;
+    for (int64_t w0 = 0; w0 < rows_kept; w0 += W) {
+      mv.w0 = w0;
+      mv.cnt = (int)std::min<int64_t>(W, rows_kept - w0);
+      HIPP(c, pre, launch_rebase_move(st, mv));
+    }
+    HIPP(c, pre, launch_rebase_commit(st, hdr, nk, c->tree, c->nn));
+    HIPP(c, pre, hipEventRecord(ev1, st));
+    HIPP(c, pre, hipStreamSynchronize(st));  // (the scratch is freed on return)
+  }
+  HIPP(c, pre, hipEventElapsedTime(&ms, ev0, ev1));
+  c->n_nodes = nk;
+  c->n_rows = rows_kept;
+  bbox_reset(c);  // the search frame follows the tree's new extent
+  bbox_add(c, h_box[0], h_box[1], h_box[2], h_box[3]);
+  info.outcome = CLRRT_REBASE_KEPT;
+  info.depth = depth;
+  info.nodes_kept = nk;
+  info.rows_kept = rows_kept;
+  info.device_ms = ms;
+  if (out) *out = info;
+  return CLRRT_OK;
 }
 
 int clrrt_exact_stats(clrrt_ctx* c, int64_t out[10]) {
@@ -1482,6 +1656,7 @@ int clrrt_tree_init_from_path(clrrt_ctx* c, const double car_state[6], int32_t* 
   if (out[0] < 0) return fail(c, CLRRT_ECAPACITY, "tree_init_from_path: tree capacity");
   c->n_nodes = out[1];
   c->n_rows = out[2];
+  c->tree_rowless = false;
   bbox_reset(c);
   HIPC(c, launch_bbox(c->stream, c->tree, nullptr, (int)c->n_nodes, c->d_bbox));
   HIPC(c, hipMemcpyAsync(c->h_bbox, c->d_bbox, sizeof(double) * 4, hipMemcpyDeviceToHost, c->stream));
@@ -1671,6 +1846,8 @@ int clrrt_set_option(clrrt_ctx* c, const char* key, int64_t value) {
     c->def.T = (int)value;
   }
   else if (k == "stream_prio") c->stream_prio = value != 0;
+  // clrrt_tree_rebase moves rows through a scratch window of this many rows (at most 64 MiB; results do not depend on it)
+  else if (k == "rebase_window_rows" && value >= 1 && value <= 838860) c->rebase_window_rows = value;
   else return fail(c, CLRRT_EINVAL, "unknown option or value: " + k);
   return CLRRT_OK;
 }

@@ -465,4 +465,57 @@ hipError_t launch_path_transform(hipStream_t st, clrrt_node* nodes, int n, doubl
 hipError_t launch_tree_reinit(hipStream_t st, const ReinitArgs& a);
 hipError_t launch_init_root(hipStream_t st, const double* state, clrrt_node* tree, NnRec* nn, double* arena);
 
+// clrrt_tree_rebase (include/clrrt.h; the kernels' comments in clrrt_kernels.hip say what each pass does).
+struct RebaseCheck {
+  RollArgs a;  // the query: parameters, obstacle tables and grid, occupancy maps, arena
+  int n;
+  int root;
+  int64_t n_rows;
+  double P0, P1, P2, t_shift;
+  const int64_t* roff;  // [n] row offsets
+  const int* nrw;       // [n] row counts
+  int* nflag;           // [n] bit 0: an invalid row, bit 1: a goal row (zeroed by the caller)
+  double* terms;        // [n_rows][tstride]: term (, lane term)
+  int tstride;
+};
+struct RebaseHdr {
+  const clrrt_node* tree;
+  int n, root, rank;
+  double P0, P1, P2, t_shift;
+  const uint64_t* packed;
+  const uint64_t* scanned;
+  const int* hop;
+  const int* nflag;
+  clrrt_node* hdr;  // [kept] new headers
+  int64_t* src;     // [kept] first source row
+  int64_t* noff;    // [kept] new row offset
+  int* lvl;         // [kept] level (root 0)
+  double* bbox;     // [4]
+  int* err;
+};
+struct RebaseMove {
+  const int64_t* noff;
+  const int64_t* src;
+  int nk;
+  int64_t w0;
+  int cnt;
+  double P0, P1, P2, t_shift;
+  double* arena;
+  double* win;  // [cnt][10]
+};
+hipError_t launch_rebase_prep(hipStream_t st, const clrrt_node* tree, int n, int64_t n_rows, int root, int64_t* roff,
+                              int* nrw, int* jump, int* hop, int* err);
+hipError_t launch_rebase_check(hipStream_t st, const RebaseCheck& a);
+hipError_t launch_rebase_double(hipStream_t st, int n, int root, const int* jin, const int* hin, const int* bin,
+                                int* jout, int* hout, int* bout, int* moved);
+// mark + the exclusive scan of packed into scanned (tmp: compact_scan_bytes(n))
+hipError_t launch_rebase_mark(hipStream_t st, int n, int root, const int* jump, const int* hop, const int* bad,
+                              const int* nflag, const int* nrw, uint64_t* packed, uint64_t* scanned,
+                              unsigned long long* stats, void* tmp, size_t tmp_bytes);
+hipError_t launch_rebase_headers(hipStream_t st, const RebaseHdr& a);
+hipError_t launch_rebase_cost(hipStream_t st, int nk, int level, const int* lvl, const int64_t* src,
+                              const double* terms, int tstride, int bend, clrrt_node* hdr);
+hipError_t launch_rebase_move(hipStream_t st, const RebaseMove& a);  // one window: gather, then scatter
+hipError_t launch_rebase_commit(hipStream_t st, const clrrt_node* hdr, int nk, clrrt_node* tree, NnRec* nn);
+
 }  // namespace clrrt

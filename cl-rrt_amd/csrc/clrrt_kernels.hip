@@ -2641,6 +2641,40 @@ __global__ void __launch_bounds__(256) k_path_transform(clrrt_node* __restrict__
   }
 }
 
+// One trajectory row x (x0 .. x6: columns 0..4 and 6) of initializeTree under the query's parameters: the :60-69 goal
+// test, checkObsDistance (:72-81, the value returned) and getNodeCost's per-row terms (:104-119; term takes the
+// occupancy clearance where it is on).  Shared by k_tree_reinit and k_rebase_check.  Without NEED_GAP only the
+// decision Dobs == 0 is exact, which is all the terms read when use_exp is off or the collision mode is the stub.
+// x: the row (10 doubles; the callers' own copy or the row in memory).  on_goal() / on_hit() run where the row passes
+// the goal test / collides; the value is the term, the lane term is reinit_lane's.
+template <bool NEED_GAP, bool OCC, class OnGoal, class OnHit>
+__device__ __forceinline__ double reinit_row(const DevParams& p, const ObsView& ov, OccView& oc, const double* x,
+                                             OnGoal on_goal, OnHit on_hit) {
+  const double ex = x[0] - p.g0;
+  const double Dgoal = sqrt(ex * ex + x[1] * x[1]);
+  const double Hgoal = fabs(x[2] - p.g2);
+  const double dVgoal = fabs(x[4] - p.g3);
+  if ((Dgoal <= 1) && (Hgoal <= 0.05) && (dVgoal <= 0.1)) on_goal();
+  Roll r;
+  r.x0 = x[0]; r.x1 = x[1]; r.x2 = x[2]; r.x6 = x[6];
+  glibc::sincos(r.x2, r.s2, r.c2);
+  uint32_t tests = 0;
+  double Dobs;
+  if constexpr (OCC) Dobs = obs_distance_occ<NEED_GAP>(r, p, ov, oc, tests);
+  else Dobs = obs_distance<NEED_GAP>(r, p, ov, tests);
+  if (Dobs == 0) on_hit();
+  double Dcost = Dobs;
+  if constexpr (OCC)
+    if (p.use_exp) Dcost = occ_cost_gap(oc, Dobs, r.x0 + 1.424 * r.c2, r.x1 + 1.424 * r.s2, r.x2, r.c2, r.s2);
+  const double kappa = glibc::tan(x[3]) / p.L;
+  double term = p.W0 * x[4] * p.dt + p.W1 * fabs(kappa);
+  if (p.use_exp) term = term + p.W2 * glibc::exp(-p.W3 * Dcost);  // glibc's exp, restated
+  return term;
+}
+__device__ __forceinline__ double reinit_lane(const DevParams& p, const double* x) {
+  return p.bend ? p.W4 * dist_to_lane(x[0], x[1], p.lane_shift0, p.Cxy1, p.Cxy2) : 0.0;
+}
+
 // initializeTree rrtplanner.cpp:39-95 + getNodeCost :104-119, one workgroup (a committed path is
 // a few nodes / a few thousand rows: latency, not throughput).  Row checks run across the block;
 // the cost recurrence (costS float, read back as the next node's double parent cost) on lane 0.
@@ -2690,28 +2724,10 @@ __global__ void __launch_bounds__(256) k_tree_reinit(ReinitArgs a) {
     const clrrt_node& h = a.pn[a.kidx[k]];
     for (int i = tid; i < h.nrows; i += blockDim.x) {
       const double* x = a.prow + (h.row_offset + i) * 10;
-      const double ex = x[0] - p.g0;
-      const double Dgoal = sqrt(ex * ex + x[1] * x[1]);
-      const double Hgoal = fabs(x[2] - p.g2);
-      const double dVgoal = fabs(x[4] - p.g3);
-      if ((Dgoal <= 1) && (Hgoal <= 0.05) && (dVgoal <= 0.1)) goal[k] = 1;
-      Roll r;
-      r.x0 = x[0]; r.x1 = x[1]; r.x2 = x[2]; r.x6 = x[6];
-      glibc::sincos(r.x2, r.s2, r.c2);
-      uint32_t tests = 0;
-      double Dobs;
-      if constexpr (OCC) Dobs = obs_distance_occ<true>(r, p, ov, oc, tests);
-      else Dobs = obs_distance<true>(r, p, ov, tests);
-      if (Dobs == 0) s_coll = 1;
-      double Dcost = Dobs;
-      if constexpr (OCC)
-        if (p.use_exp) Dcost = occ_cost_gap(oc, Dobs, r.x0 + 1.424 * r.c2, r.x1 + 1.424 * r.s2, r.x2, r.c2, r.s2);
-      const double kappa = glibc::tan(x[3]) / p.L;
-      double term = p.W0 * x[4] * p.dt + p.W1 * fabs(kappa);
-      if (p.use_exp) term = term + p.W2 * glibc::exp(-p.W3 * Dcost);  // glibc's exp, restated
+      const double term = reinit_row<true, OCC>(p, ov, oc, x, [&] { goal[k] = 1; }, [&] { s_coll = 1; });
       double* t = a.terms + (a.koff[k] + i) * 2;
       t[0] = term;
-      t[1] = p.bend ? p.W4 * dist_to_lane(x[0], x[1], p.lane_shift0, p.Cxy1, p.Cxy2) : 0.0;
+      t[1] = reinit_lane(p, x);
     }
   }
   __syncthreads();
@@ -2761,6 +2777,260 @@ __global__ void __launch_bounds__(256) k_tree_reinit(ReinitArgs a) {
     for (int e = tid; e < h.nrows * 10; e += blockDim.x) dst[e] = src[e];
   }
   if (tid == 0) { a.out[0] = CLRRT_REINIT_KEPT; a.out[1] = kept; a.out[2] = rows; }
+}
+
+// ----------------------------------------------------------------- clrrt_tree_rebase (include/clrrt.h)
+// The tree carried into the next query: the subtree of node `root`, transformed into the new car frame, re-checked
+// row by row against the current scene, compacted and re-costed.  Nothing here writes the tree, the mirror or the
+// arena before the host knows the outcome: prep, check, closure, mark, scan, headers and costs work in scratch; the
+// row move and k_rebase_commit run last.  No kernel waits for another wave's result.
+//
+// Largest k in [lo, hi] with v[k] <= x (lo when there is none).
+__device__ __forceinline__ int last_le(const int64_t* __restrict__ v, int lo, int hi, int64_t x) {
+  while (lo < hi) {
+    const int mid = lo + (hi - lo + 1) / 2;
+    if (v[mid] <= x) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+// The nodes a block's 256 consecutive rows [first, first + 256) can belong to: two lanes search the whole offset
+// array, every lane then searches between their results (a handful of nodes: rows per node run from 1 to 1001).
+__device__ __forceinline__ void block_node_range(const int64_t* __restrict__ off, int n, int64_t first, int64_t last,
+                                                 int& lo, int& hi) {
+  __shared__ int s_range[2];
+  if (threadIdx.x == 0) s_range[0] = last_le(off, 0, n - 1, first);
+  if (threadIdx.x == 64) s_range[1] = last_le(off, 0, n - 1, last);
+  __syncthreads();
+  lo = s_range[0];
+  hi = s_range[1];
+}
+
+// One lane per node: the compact arrays the later passes read (row offsets, row counts, the closure's start: jump =
+// parent, stopping at the root (-1 for the root itself), hop = levels to jump) and the layout the call relies on --
+// parents precede children, every node has rows, rows lie in node order without overlap (err: first violation kind).
+__global__ void __launch_bounds__(256) k_rebase_prep(const clrrt_node* __restrict__ tree, int n, int64_t n_rows, int root,
+                                                     int64_t* __restrict__ roff, int* __restrict__ nrw,
+                                                     int* __restrict__ jump, int* __restrict__ hop, int* __restrict__ err) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n) return;
+  const int p = tree[k].parent, nr = tree[k].nrows;
+  const int64_t ro = tree[k].row_offset;
+  roff[k] = ro;
+  nrw[k] = nr;
+  jump[k] = k == root ? -1 : p;
+  hop[k] = (k == root || p < 0) ? 0 : 1;
+  const int64_t next = k + 1 < n ? tree[k + 1].row_offset : n_rows;
+  if (p < -1 || p >= k) atomicMax(err, 1);
+  else if (nr < 1 || ro < 0 || ro + nr > next) atomicMax(err, 2);
+}
+
+// The hot kernel: one lane per row of the arena.  Rows are laid out in node order, so a block's rows belong to a short
+// run of nodes (block_node_range) and each lane finds its node by a search of one or two steps.  The row is transformed
+// in registers (point_world_to_car, heading - pose[2], time - t_shift), then takes re-init's row function: the
+// collision decision of the current mode on the obstacle tables and grid staged in LDS (without NEED_GAP; with it the
+// exhaustive scan, whose gap the cost term needs), the cost terms and the goal bit.  Flags go to the node with one
+// atomic per node per wave: bit 0 an invalid row, bit 1 a goal row.  Nodes before the root cannot be in its subtree and
+// are skipped; the root is checked on its last row alone (the one it keeps).
+template <bool NEED_GAP, bool OCC>
+__global__ void __launch_bounds__(256) k_rebase_check(RebaseCheck ra) {
+  extern __shared__ float4 lds[];
+  glibc::stage_tables();
+  const RollArgs& a = ra.a;
+  const ObsView ov = stage_obstacles<NEED_GAP>(a, lds);
+  OccView oc{};
+  if constexpr (OCC) oc = occ_stage(a.occ, lds);
+  CLRRT_PARAMS_DECL(P);
+  double sn, cs;
+  glibc::sincos(ra.P2, sn, cs);
+  const int64_t first = (int64_t)blockIdx.x * 256;
+  const int64_t last = first + 255 < ra.n_rows ? first + 255 : ra.n_rows - 1;
+  int lo, hi;
+  block_node_range(ra.roff, ra.n, first, last, lo, hi);
+  if (hi < ra.root) return;  // (block-uniform)
+  const int64_t row = first + threadIdx.x;
+  int node = -1;
+  bool act = false;
+  if (row < ra.n_rows) {
+    node = last_le(ra.roff, lo, hi, row);
+    const int64_t ro = ra.roff[node];
+    const int nr = ra.nrw[node];
+    act = node >= ra.root && row >= ro && row < ro + nr && (node != ra.root || row == ro + nr - 1);
+  }
+  int f = 0;
+  if (act) {
+    const double* src = a.arena + row * 10;
+    double x[7];  // (registers: columns 0..6, the ones the row function reads)
+#pragma unroll
+    for (int q = 0; q < 7; q++) x[q] = src[q];
+    point_world_to_car(x[0], x[1], ra.P0, ra.P1, sn, cs);
+    x[2] -= ra.P2;
+    x[6] -= ra.t_shift;
+    const double term = reinit_row<NEED_GAP, OCC>(P, ov, oc, x, [&] { f |= 2; }, [&] { f |= 1; });
+    ra.terms[row * ra.tstride] = term;
+    if (ra.tstride > 1) ra.terms[row * ra.tstride + 1] = reinit_lane(P, x);
+  }
+  unsigned long long todo = __ballot(act && f != 0);
+  while (todo) {  // (wave-uniform: one turn per node of the wave that has a flag to set)
+    const int lead = __ffsll((long long)todo) - 1;
+    const int nd = __shfl(node, lead);
+    const bool mine = act && node == nd;
+    const unsigned long long same = __ballot(mine);
+    const unsigned long long bad = __ballot(mine && (f & 1)), gl = __ballot(mine && (f & 2));
+    if ((int)(threadIdx.x & 63) == lead) atomicOr(&ra.nflag[nd], (bad ? 1 : 0) | (gl ? 2 : 0));
+    todo &= ~same;
+  }
+}
+
+// Descendant closure and depth by pointer doubling, double-buffered (one launch per pass, ceil(log2 depth) + 1 passes:
+// the last finds nothing to do).  A node whose jump is the root or -1 has stopped; any other takes its jump's state:
+// bad |= bad[jump] (bit 0; the first pass reads the check's flags), hop += hop[jump], jump = jump[jump].  bad[k] is
+// then the OR over the chain from k up to, not including, the root.
+__global__ void __launch_bounds__(256) k_rebase_double(int n, int root, const int* __restrict__ jin,
+                                                       const int* __restrict__ hin, const int* __restrict__ bin,
+                                                       int* __restrict__ jout, int* __restrict__ hout,
+                                                       int* __restrict__ bout, int* __restrict__ moved) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n) return;
+  const int j = jin[k];
+  int b = bin[k] & 1, h = hin[k], jn = j;
+  if (j >= 0 && j != root) {
+    b |= bin[j] & 1;
+    h += hin[j];
+    jn = jin[j];
+    *moved = 1;
+  }
+  jout[k] = jn;
+  hout[k] = h;
+  bout[k] = b;
+}
+
+// Kept set: the root, and every subtree node (jump == root) with no invalid row on its chain below the root.  packed =
+// rows << 32 | 1 for a kept node (the root keeps one row), whose exclusive scan gives new id and new row offset.
+// stats: [0] subtree nodes, [1] subtree nodes below the root with an invalid row of their own, [2] levels kept.
+__global__ void __launch_bounds__(256) k_rebase_mark(int n, int root, const int* __restrict__ jump,
+                                                     const int* __restrict__ hop, const int* __restrict__ bad,
+                                                     const int* __restrict__ nflag, const int* __restrict__ nrw,
+                                                     uint64_t* __restrict__ packed,
+                                                     unsigned long long* __restrict__ stats) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool in = k < n;
+  const bool sub = in && (k == root || jump[k] == root);
+  const bool keep = sub && (k == root || !(bad[k] & 1));
+  const bool coll = sub && k != root && (nflag[k] & 1);
+  if (in) packed[k] = keep ? ((uint64_t)(k == root ? 1 : nrw[k]) << 32) | 1ull : 0ull;
+  int d = keep ? hop[k] + 1 : 0;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) d = max(d, __shfl_xor(d, o, 64));
+  const unsigned long long ms = __ballot(sub), mc = __ballot(coll);
+  if ((threadIdx.x & 63) == 0) {
+    if (ms) atomicAdd(&stats[0], (unsigned long long)__popcll(ms));
+    if (mc) atomicAdd(&stats[1], (unsigned long long)__popcll(mc));
+    if (d) atomicMax(&stats[2], (unsigned long long)d);
+  }
+}
+
+// New headers of the kept nodes, into scratch: transformed exactly as k_path_transform's world-to-car branch, time
+// shifted, parent remapped, costE relative to the root's, goal from the check, rows at their compacted offset.  src[i]:
+// where the node's rows lie now (the root: its last row), noff[i] their new offset, lvl[i] the node's level.  The box of
+// the new positions goes to bbox (preset to +inf, +inf, -inf, -inf), one atomic per wave and bound.
+__global__ void __launch_bounds__(256) k_rebase_headers(RebaseHdr a) {
+  glibc::stage_tables();
+  double s, c;
+  glibc::sincos(a.P2, s, c);
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool keep = k < a.n && a.packed[k] != 0;
+  double bx0 = HUGE_VAL, by0 = HUGE_VAL, bx1 = -HUGE_VAL, by1 = -HUGE_VAL;
+  if (keep) {
+    const int i = (int)(a.scanned[k] & 0xffffffffull);
+    const int64_t off = (int64_t)(a.scanned[k] >> 32);
+    clrrt_node d = a.tree[k];
+    const int64_t from = k == a.root ? d.row_offset + d.nrows - 1 : d.row_offset;
+    if (off > from) atomicMax(a.err, 3);  // (the in-place move needs destinations at or below their sources)
+    point_world_to_car(d.state[0], d.state[1], a.P0, a.P1, s, c);
+    d.state[2] -= a.P2;
+    point_world_to_car(d.ref_front[0], d.ref_front[1], a.P0, a.P1, s, c);
+    point_world_to_car(d.ref_back[0], d.ref_back[1], a.P0, a.P1, s, c);
+    d.ang_par = node_ang_par(d.ref_back[0], d.ref_back[1], d.ref_front[0], d.ref_front[1]);
+    d.state[6] = d.state[6] - a.t_shift;
+    d.costE = (float)((double)d.costE - (double)a.tree[a.root].costE);
+    d.parent = k == a.root ? -1 : (int)(a.scanned[d.parent] & 0xffffffffull);
+    d.goal = (a.nflag[k] >> 1) & 1;
+    if (k == a.root) d.nrows = 1;
+    d.row_offset = off;
+    d.owner = a.rank;
+    a.hdr[i] = d;
+    a.src[i] = from;
+    a.noff[i] = off;
+    a.lvl[i] = a.hop[k];
+    if (isfinite(d.state[0]) && isfinite(d.state[1])) { bx0 = bx1 = d.state[0]; by0 = by1 = d.state[1]; }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    bx0 = fmin(bx0, __shfl_xor(bx0, o, 64)); by0 = fmin(by0, __shfl_xor(by0, o, 64));
+    bx1 = fmax(bx1, __shfl_xor(bx1, o, 64)); by1 = fmax(by1, __shfl_xor(by1, o, 64));
+  }
+  if ((threadIdx.x & 63) == 0 && bx0 <= bx1) {
+    atomicMin(&a.bbox[0], bx0); atomicMin(&a.bbox[1], by0);
+    atomicMax(&a.bbox[2], bx1); atomicMax(&a.bbox[3], by1);
+  }
+}
+
+// The cost recurrence of one level (one launch per level, in stream order, so the parents' costS are there): re-init's
+// sum, cost = (double) costS[parent] (0 for the root), then per row in row order cost += term and, with bend, cost +=
+// lane term; costS = (float) cost.
+__global__ void __launch_bounds__(256) k_rebase_cost(int nk, int level, const int* __restrict__ lvl,
+                                                     const int64_t* __restrict__ src, const double* __restrict__ terms,
+                                                     int tstride, int bend, clrrt_node* hdr) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nk || lvl[i] != level) return;
+  double cost = level == 0 ? 0.0 : (double)hdr[hdr[i].parent].costS;
+  const double* t = terms + src[i] * tstride;
+  const int nr = hdr[i].nrows;
+  for (int r = 0; r < nr; r++) {
+    cost += t[(int64_t)r * tstride];
+    if (bend) cost += t[(int64_t)r * tstride + 1];
+  }
+  hdr[i].costS = (float)cost;
+}
+
+// The in-place row move, one window of destination rows [w0, w0 + cnt) at a time: gather (with the row transform) into
+// the bounded scratch, then scratch to destination, in stream order.  A destination never lies above its source and
+// sources ascend with destinations, so a window's stores touch no row a later window still has to read.
+__global__ void __launch_bounds__(256) k_rebase_gather(RebaseMove a) {
+  glibc::stage_tables();
+  double s, c;
+  glibc::sincos(a.P2, s, c);
+  const int64_t first = a.w0 + (int64_t)blockIdx.x * 256;
+  const int64_t end = a.w0 + a.cnt;
+  int lo, hi;
+  block_node_range(a.noff, a.nk, first, first + 255 < end ? first + 255 : end - 1, lo, hi);
+  const int64_t d = first + threadIdx.x;
+  if (d >= end) return;
+  const int i = last_le(a.noff, lo, hi, d);
+  const double* x = a.arena + (a.src[i] + (d - a.noff[i])) * 10;
+  double r[10];
+#pragma unroll
+  for (int q = 0; q < 10; q++) r[q] = x[q];
+  point_world_to_car(r[0], r[1], a.P0, a.P1, s, c);
+  r[2] -= a.P2;
+  r[6] -= a.t_shift;
+  double* o = a.win + (d - a.w0) * 10;
+#pragma unroll
+  for (int q = 0; q < 10; q++) o[q] = r[q];
+}
+__global__ void __launch_bounds__(256) k_rebase_scatter(const double* __restrict__ win, int64_t n, double* __restrict__ dst) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e < n) dst[e] = win[e];
+}
+
+// The new headers into the tree, and their nearest-node records into the mirror.
+__global__ void __launch_bounds__(256) k_rebase_commit(const clrrt_node* __restrict__ hdr, int nk, clrrt_node* tree,
+                                                       NnRec* nn) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nk) return;
+  const clrrt_node d = hdr[i];
+  tree[i] = d;
+  nn[i] = nn_record(d, i);
 }
 
 // Elementary functions as the kernels evaluate them (test hook: bit-compared with the host libm).
@@ -3665,6 +3935,78 @@ hipError_t launch_tree_reinit(hipStream_t st, const ReinitArgs& a) {
     hipLaunchKernelGGL(k_tree_reinit<true>, dim3(1), dim3(256), 0, st, a);
   else
     hipLaunchKernelGGL(k_tree_reinit<false>, dim3(1), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_rebase_prep(hipStream_t st, const clrrt_node* tree, int n, int64_t n_rows, int root, int64_t* roff,
+                              int* nrw, int* jump, int* hop, int* err) {
+  hipLaunchKernelGGL(k_rebase_prep, dim3((n + 255) / 256), dim3(256), 0, st, tree, n, n_rows, root, roff, nrw, jump,
+                     hop, err);
+  return hipGetLastError();
+}
+
+// The LDS of a rollout launch of the same query: the obstacle tables (not with need_gap), then the occupancy maps
+// where they fit (launch_roll_occ).
+hipError_t launch_rebase_check(hipStream_t st, const RebaseCheck& a0) {
+  if (a0.n_rows <= 0) return hipSuccess;
+  RebaseCheck a = a0;
+  const bool gap = a.a.p.need_gap, occ = a.a.occ.w > 0;
+  const size_t lds = occ_place(a.a.occ, gap ? 0 : roll_lds_bytes(a.a), false);
+  const void* fn = occ ? (gap ? (const void*)&k_rebase_check<true, true> : (const void*)&k_rebase_check<false, true>)
+                       : (gap ? (const void*)&k_rebase_check<true, false> : (const void*)&k_rebase_check<false, false>);
+  if (lds > 64 * 1024) {
+    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
+  const dim3 grid((unsigned)((a.n_rows + 255) / 256)), block(256);
+  if (occ && gap) hipLaunchKernelGGL((k_rebase_check<true, true>), grid, block, lds, st, a);
+  else if (occ) hipLaunchKernelGGL((k_rebase_check<false, true>), grid, block, lds, st, a);
+  else if (gap) hipLaunchKernelGGL((k_rebase_check<true, false>), grid, block, lds, st, a);
+  else hipLaunchKernelGGL((k_rebase_check<false, false>), grid, block, lds, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_rebase_double(hipStream_t st, int n, int root, const int* jin, const int* hin, const int* bin,
+                                int* jout, int* hout, int* bout, int* moved) {
+  hipLaunchKernelGGL(k_rebase_double, dim3((n + 255) / 256), dim3(256), 0, st, n, root, jin, hin, bin, jout, hout,
+                     bout, moved);
+  return hipGetLastError();
+}
+
+hipError_t launch_rebase_mark(hipStream_t st, int n, int root, const int* jump, const int* hop, const int* bad,
+                              const int* nflag, const int* nrw, uint64_t* packed, uint64_t* scanned,
+                              unsigned long long* stats, void* tmp, size_t tmp_bytes) {
+  hipLaunchKernelGGL(k_rebase_mark, dim3((n + 255) / 256), dim3(256), 0, st, n, root, jump, hop, bad, nflag, nrw,
+                     packed, stats);
+  LAUNCH_CHECK();
+  size_t bytes = tmp_bytes;
+  return hipcub::DeviceScan::ExclusiveSum(tmp, bytes, packed, scanned, n, st);
+}
+
+hipError_t launch_rebase_headers(hipStream_t st, const RebaseHdr& a) {
+  hipLaunchKernelGGL(k_rebase_headers, dim3((a.n + 255) / 256), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_rebase_cost(hipStream_t st, int nk, int level, const int* lvl, const int64_t* src,
+                              const double* terms, int tstride, int bend, clrrt_node* hdr) {
+  hipLaunchKernelGGL(k_rebase_cost, dim3((nk + 255) / 256), dim3(256), 0, st, nk, level, lvl, src, terms, tstride,
+                     bend, hdr);
+  return hipGetLastError();
+}
+
+hipError_t launch_rebase_move(hipStream_t st, const RebaseMove& a) {
+  if (a.cnt <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_rebase_gather, dim3((a.cnt + 255) / 256), dim3(256), 0, st, a);
+  LAUNCH_CHECK();
+  const int64_t ne = (int64_t)a.cnt * 10;
+  hipLaunchKernelGGL(k_rebase_scatter, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, st, a.win, ne,
+                     a.arena + a.w0 * 10);
+  return hipGetLastError();
+}
+
+hipError_t launch_rebase_commit(hipStream_t st, const clrrt_node* hdr, int nk, clrrt_node* tree, NnRec* nn) {
+  hipLaunchKernelGGL(k_rebase_commit, dim3((nk + 255) / 256), dim3(256), 0, st, hdr, nk, tree, nn);
   return hipGetLastError();
 }
 

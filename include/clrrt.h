@@ -305,6 +305,52 @@ int clrrt_tree_rows(clrrt_ctx* ctx, int64_t row_offset, int64_t nrows, double* o
 /* Engine extension (no reference counterpart): drop the nodes [n, size) appended last (and their rows), e.g. the
  * iterations a caller speculated but did not take (clrrt_adapter's dropin::expandTree cache). 1 <= n <= size. */
 int clrrt_tree_truncate(clrrt_ctx* ctx, int64_t n);
+/* Engine extension (no reference counterpart; the reference's initializeTree keeps the committed path only): carry the
+ * tree into the next replanning query.  The tree becomes the subtree of node root_id, expressed in the car frame
+ * `pose` (x, y, heading of the new car in the frame the tree is in now), with times shifted by t_shift, re-checked
+ * against the context's current scene, compacted and re-costed, all on the device.  Off unless called: no other
+ * result or launch depends on it.  Everything is double arithmetic without FMA contraction.
+ *   Subtree.  Node root_id and every node whose parent chain reaches it (parents precede their children).
+ *   Transform, evaluated before anything is written.  Headers exactly as clrrt_path_transform(CLRRT_WORLD_TO_CAR,
+ * pose) transforms them: state[0..2], ref_front, ref_back, ang_par recomputed; state[6] becomes state[6] - t_shift.
+ * Rows: (x, y) through transformPointWorldToCar, row[2] -= pose[2], row[6] -= t_shift.  The row heading IS transformed
+ * here, unlike the reference's transformNodes* (and clrrt_path_transform), which leave row headings in the frame of
+ * the query that grew them: revalidation needs the true heading.
+ *   Root.  It keeps only its last row, as a fresh root has one row: nrows = 1, parent = -1, costE = 0.
+ *   Revalidation.  A node is invalid when any of its transformed rows has checkObsDistance == 0 under the context's
+ * current parameters, collision mode, obstacles, occupancy grid and obs_use_pred: the value clrrt_obstacle_distance
+ * returns for that row.  Rows with non-finite coordinates do not hit.  If the root's one row is invalid the outcome
+ * is CLRRT_REBASE_ROOT_COLLIDES and nothing has been written: tree, rows, counters and search state are bit for bit
+ * as before.  Otherwise the kept set is the root plus every subtree node that is valid and whose parent is kept.
+ *   Renumbering.  Kept nodes keep their relative order; the new id is the rank among the kept nodes (the root: 0),
+ * parent is remapped, rows are compacted in node order from arena row 0, owner is the context's rank.
+ *   Costs and flags.  costE' = (float)((double)costE - (double)costE[root_id]).  goal and costS are redone as
+ * clrrt_tree_init_from_path redoes them for a chain: goal = 1 when some row passes initializeTree's goal test
+ * (rrtplanner.cpp:60-69) against the current goal; costS' = (float)cost with cost = (double)costS'[parent] (0.0 for
+ * the root), then for each row in row order cost += term and, with bend, cost += lane term -- re-init's terms,
+ * the occupancy clearance included where re-init applies it.  So costS' of node k is what clrrt_tree_init_from_path
+ * gives k when the chain root -> k of the rebased tree is the committed path and every node survives its filter.
+ *   State.  Legal only between expansions.  It first lands deferred rows, then drops prefetched searches, kept
+ * walk indexes and pending replays as clrrt_tree_truncate does, and takes the search frame from the kept nodes'
+ * extent; the next expansion rebuilds its index.  clrrt_get_counters is untouched.  The rows move in place through a
+ * scratch window of option "rebase_window_rows" rows (default 786432: 60 MiB; at most 838860), so the call works on a
+ * full arena; beside it the call holds 8 bytes (16 with bend) per row of the tree for the cost terms while it runs.
+ *   Errors.  CLRRT_EINVAL: root_id outside the tree, a non-finite pose or t_shift.  CLRRT_ESTATE: clrrt_set_shards
+ * with world > 1 (sharded carry-over is not supported); a tree without rows (clrrt_tree_load, and whatever grew from
+ * it); rows not laid out in node order.
+ * info: nodes_subtree counts the subtree with its root; nodes_collided the subtree nodes below the root with an
+ * invalid row of their own (their descendants are dropped without being counted); depth the levels of the kept tree;
+ * device_ms the event time from the call's first to its last kernel.  `out` may be NULL. */
+#define CLRRT_REBASE_KEPT 0           /* the tree is now the surviving subtree */
+#define CLRRT_REBASE_ROOT_COLLIDES 1  /* the new root's row collides: tree left exactly as it was */
+typedef struct {
+  int32_t outcome;
+  int32_t depth;          /* levels of the kept tree (root = 1) */
+  int64_t nodes_before, nodes_subtree, nodes_collided, nodes_kept;
+  int64_t rows_before, rows_kept;
+  double  device_ms;      /* event time of the call's kernels */
+} clrrt_rebase_info;
+int clrrt_tree_rebase(clrrt_ctx* ctx, int64_t root_id, const double pose[3], double t_shift, clrrt_rebase_info* out);
 
 /* Per-iteration record of the expandTree iterations an expansion commits, in iteration order (clrrt_iteration_log
  * on; EXACT rounds and BATCH rounds without deferred samples): the nodes the iteration appended (0, 1 regular, 2
@@ -617,8 +663,8 @@ int clrrt_work_counters(clrrt_ctx* ctx, int64_t out[3]);
  * family measured with HIP events on the stream each launch runs on.  which: 0 = nn (index builds,
  * walk searches, merges), 1 = rollout, 2 = commit, 3 = the walk searches alone (part of 0), 4 = the main
  * stream's waits for the side streams' lists (the search's share of the round's critical path), 5 = sharded
- * exchanges (the stream span from the records' copy to the gathered records); returns the summed ms and the
- * launch (or wait) count. */
+ * exchanges (the stream span from the records' copy to the gathered records), 6 = clrrt_tree_rebase's check kernel
+ * (one lane per row: rows x 80 B read); returns the summed ms and the launch (or wait) count. */
 int clrrt_kernel_time(clrrt_ctx* ctx, int32_t which, double* ms, int64_t* launches);
 int clrrt_enable_timing(clrrt_ctx* ctx, int32_t on);
 

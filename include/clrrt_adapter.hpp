@@ -747,6 +747,9 @@ struct PlanReport {
   int64_t counters[4] = {0, 0, 0, 0};  /* sim_count, fail_collision, fail_acclimit, fail_iterlimit (:9, :45) */
   int64_t rows_fetched = 0;     /* rows the path completer took from other ranks (0 without one) */
   int64_t deferred = 0;         /* clrrt_stats::deferred of the expansion (option "defer_steps"; per rank when sharded) */
+  bool carried = false;         /* Config::carry_tree: the query started from the rebased tree (`rebase` is its info) */
+  clrrt_rebase_info rebase = {};
+  int64_t start_size = 0;       /* tree nodes before the expansion */
 };
 
 class MotionPlanner {
@@ -761,6 +764,11 @@ class MotionPlanner {
     double budget_ms = 200;     /* Timer(200) */
     int64_t n_iters = 0;        /* > 0: a fixed iteration count instead of the budget (reproducible runs) */
     bool draw_tree = false;
+    /* Engine extension (default off: nothing changes): keep the tree between queries (clrrt_tree_rebase) instead of
+     * cutting it down to the committed path.  The new root is the first committed-path node initializeTree's filter
+     * would keep (its last row has x >= 0 in the new car frame); without one, or when its row collides, the query
+     * falls back to initializeTree.  Needs commit_path; not supported under sharding. */
+    bool carry_tree = false;
   };
 
   MotionPlanner(const Config& c, uint32_t seed, int device = 0) : cfg_(c) {
@@ -848,7 +856,12 @@ class MotionPlanner {
     check(ctx_, clrrt_path_transform(ctx_, CLRRT_WORLD_TO_CAR, world), "clrrt_path_transform");          // :22
     if (!cfg_.commit_path) check(ctx_, clrrt_path_commit(ctx_, nullptr, 0, nullptr), "clrrt_path_commit");  // :28-30
     int32_t oc = -1;
-    check(ctx_, clrrt_tree_init_from_path(ctx_, car, &oc), "clrrt_tree_init_from_path");                   // :32
+    clrrt_rebase_info rb = {};
+    const bool carried = cfg_.carry_tree && cfg_.commit_path && carry_rebase(world, &rb);
+    if (carried) oc = CLRRT_REINIT_KEPT;
+    else check(ctx_, clrrt_tree_init_from_path(ctx_, car, &oc), "clrrt_tree_init_from_path");              // :32
+    int64_t start_size = 0;
+    check(ctx_, clrrt_tree_size(ctx_, &start_size, nullptr), "clrrt_tree_size");
     clrrt_stats st;
     check(ctx_, clrrt_expand(ctx_, &rng_, cfg_.n_iters, cfg_.n_iters > 0 ? 0.0 : cfg_.budget_ms, cfg_.mode,
                              cfg_.batch, &st), "clrrt_expand");                                            // :39-43
@@ -877,7 +890,11 @@ class MotionPlanner {
                   "other ranks and no path completer is set (setPathCompleter)");
     }
     check(ctx_, clrrt_path_transform(ctx_, CLRRT_CAR_TO_WORLD, world), "clrrt_path_transform");  // :54
+    if (cfg_.carry_tree) carry_remember(world, ids);
     if (rep) {
+      rep->carried = carried;
+      rep->rebase = rb;
+      rep->start_size = start_size;
       rep->rows_fetched = rows_fetched;
       rep->deferred = st.deferred;
       rep->reinit_outcome = oc;
@@ -912,6 +929,46 @@ class MotionPlanner {
   void clearPath() { check(ctx_, clrrt_path_commit(ctx_, nullptr, 0, nullptr), "clrrt_path_commit"); }
 
  private:
+  /* carry_tree: what the next query needs of the path just committed (now in the world frame): the nodes' tree ids,
+   * the (x, y) of each node's last row, its time state[6], and the pose of the frame the tree is in. */
+  void carry_remember(const double world[3], const std::vector<int32_t>& ids) {
+    carry_ids_ = ids;
+    carry_xy_.clear();
+    carry_t_.clear();
+    for (int k = 0; k < 3; k++) carry_pose_[k] = world[k];
+    int32_t n = 0;
+    int64_t nr = 0;
+    check(ctx_, clrrt_path_size(ctx_, &n, &nr), "clrrt_path_size");
+    if (n == 0) return;
+    std::vector<clrrt_node> h((size_t)n);
+    std::vector<double> rows(10 * (size_t)nr);
+    check(ctx_, clrrt_path_download(ctx_, h.data(), rows.data()), "clrrt_path_download");
+    for (const clrrt_node& nd : h) {
+      const double* r = &rows[10 * (size_t)(nd.row_offset + nd.nrows - 1)];
+      carry_xy_.push_back(r[0]);
+      carry_xy_.push_back(r[1]);
+      carry_t_.push_back(nd.state[6]);
+    }
+  }
+  /* carry_tree: rebase the tree on the first remembered path node ahead of the car (transformPointWorldToCar's x >= 0,
+   * NaN kept as initializeTree keeps it); false where the query has to fall back to initializeTree. */
+  bool carry_rebase(const double world[3], clrrt_rebase_info* rb) {
+    const double c = std::cos(world[2]), s = std::sin(world[2]);
+    for (size_t i = 0; i < carry_ids_.size() && 2 * i + 1 < carry_xy_.size(); i++) {
+      const double X = carry_xy_[2 * i], Y = carry_xy_[2 * i + 1];
+      const double xc = X * c - world[0] * c - world[1] * s + Y * s;
+      if (xc < 0) continue;
+      // the new car pose in the frame the tree is in (the previous query's car frame)
+      const double pc = std::cos(carry_pose_[2]), ps = std::sin(carry_pose_[2]);
+      const double pose[3] = {world[0] * pc - carry_pose_[0] * pc - carry_pose_[1] * ps + world[1] * ps,
+                              world[1] * pc - carry_pose_[1] * pc + carry_pose_[0] * ps - world[0] * ps,
+                              world[2] - carry_pose_[2]};
+      check(ctx_, clrrt_tree_rebase(ctx_, carry_ids_[i], pose, carry_t_[i], rb), "clrrt_tree_rebase");
+      return rb->outcome == CLRRT_REBASE_KEPT;
+    }
+    return false;
+  }
+
   void draw_tree(int64_t n_nodes, std::vector<TreeMarker>& out) {
     std::vector<clrrt_node> h((size_t)n_nodes);
     if (n_nodes) check(ctx_, clrrt_tree_download(ctx_, 0, n_nodes, h.data()), "clrrt_tree_download");
@@ -936,6 +993,9 @@ class MotionPlanner {
   bool grid_dirty_ = false;
   double clear_max_ = 0.0;
   bool clear_dirty_ = false;
+  std::vector<int32_t> carry_ids_;  /* carry_tree: the last committed path (carry_remember) */
+  std::vector<double> carry_xy_, carry_t_;
+  double carry_pose_[3] = {0, 0, 0};
   int32_t (*completer_)(void*, clrrt_ctx*, int64_t*) = nullptr;
   void* completer_user_ = nullptr;
 };

@@ -108,6 +108,8 @@ _SIGS = {
     "clrrt_obstacle_distance": (C.c_int, [C.c_void_p, P(C.c_double), C.c_int32, P(C.c_double)]),
     "clrrt_debug_counters": (C.c_int, [C.c_void_p, P(C.c_int64)]),
     "clrrt_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int64]),
+    "clrrt_debug_mem_guard": (C.c_int, [C.c_int64]),
+    "clrrt_debug_mem_check": (C.c_int, [P(abi.MemReport)]),
 }
 
 
@@ -152,6 +154,24 @@ def default_params(v0=0.0, goal=(40.0, 0.0, 0.0, 0.0), vmax=5.0, collision_mode=
         raise ClrrtError(f"clrrt_params_default -> {rc}")
     p.collision_mode = collision_mode
     return p
+
+
+def mem_guard(nbytes):
+    """clrrt_debug_mem_guard (test facility): guard bands of `nbytes` (0: off, else a multiple of 256 up to 1 MiB)
+    around every device and pinned block the library allocates from now on."""
+    rc = lib().clrrt_debug_mem_guard(int(nbytes))
+    if rc != 0:
+        raise ClrrtError(f"clrrt_debug_mem_guard({nbytes}) -> {rc}")
+
+
+def mem_check():
+    """clrrt_debug_mem_check: the guard bands of every live block, plus what the frees since the last call found, as
+    a dict of the clrrt_mem_report fields (first_side: -1 the band before the block, +1 the one after it)."""
+    r = abi.MemReport()
+    rc = lib().clrrt_debug_mem_check(C.byref(r))
+    if rc != 0:
+        raise ClrrtError(f"clrrt_debug_mem_check -> {rc}")
+    return {k: getattr(r, k) for k, _ in abi.MemReport._fields_ if k != "reserved"}
 
 
 class Rng:

@@ -75,6 +75,12 @@ class RebaseInfo(C.Structure):  # clrrt_rebase_info
                 ("rows_before", C.c_int64), ("rows_kept", C.c_int64), ("device_ms", C.c_double)]
 
 
+class MemReport(C.Structure):  # clrrt_mem_report
+    _fields_ = [("blocks_checked", C.c_int64), ("guard_bytes_checked", C.c_int64), ("violations", C.c_int64),
+                ("first_serial", C.c_int64), ("first_bytes", C.c_int64), ("first_offset", C.c_int64),
+                ("first_side", C.c_int32), ("reserved", C.c_int32)]
+
+
 class Node(C.Structure):
     _fields_ = [
         ("state", C.c_double * 10), ("ref_front", C.c_double * 2), ("ref_back", C.c_double * 2),

@@ -1729,6 +1729,21 @@ int clrrt_debug_counters(clrrt_ctx* c, int64_t out[64]) {
   return CLRRT_OK;
 }
 
+// Guard bands around every block of this library's memory owner (clrrt::MemGuard, clrrt_devmem.hpp): a test facility.
+int clrrt_debug_mem_guard(int64_t bytes) {
+  if (bytes < 0 || !clrrt::MemGuard<HipMem>::set((size_t)bytes)) return CLRRT_EINVAL;
+  return CLRRT_OK;
+}
+
+int clrrt_debug_mem_check(clrrt_mem_report* out) {
+  if (!out) return CLRRT_EINVAL;
+  clrrt::MemReport r;
+  clrrt::MemGuard<HipMem>::check(&r);  // (each band's copy-out waits for the device first)
+  *out = clrrt_mem_report{r.blocks_checked, r.guard_bytes_checked, r.violations, r.first_serial,
+                          r.first_bytes,    r.first_offset,        r.first_side, 0};
+  return CLRRT_OK;
+}
+
 int clrrt_work_counters(clrrt_ctx* c, int64_t out[3]) {
   if (!c || !out) return CLRRT_EINVAL;
   HIPC(c, hipSetDevice(c->device));
@@ -3329,7 +3344,17 @@ static int expand_end(ExpandRun& x, int rc, clrrt_rng* rng, clrrt_stats* out) {
   // rows: part of the query's output tree, so inside its time
   if (rc == CLRRT_OK) rc = defer_drain(c, &x.st.goal_nodes_added);
   x.st.deferred = c->def.deferred_total;
-  if (rc == CLRRT_OK) rc = flush_replays(c);
+  if (rc == CLRRT_OK) {
+    rc = flush_replays(c);
+  } else if (rc == CLRRT_ECAPACITY) {
+    // A refused round (or one that failed on a capacity) leaves rows of committed nodes owed: the last commit's
+    // replays and, with deferred samples, the replays the cap suspended -- they sit in the carry buffer beside the
+    // abandoned samples' chains, which shard_expansion_end and the next defer_begin forget.  They run to their end
+    // now (the abandoned chains with them; nothing selects their results).  The refusal stays the error.
+    const std::string err = c->err;
+    (void)flush_replays(c);
+    c->err = err;
+  }
   if (rc == CLRRT_OK && x.sharded) rc = shard_goal_count(c, &x.st.goal_nodes_added);
   // every stream drained, the first error kept: before the closing exchange, so a late asynchronous error travels in it
   for (hipStream_t s : {c->side, c->side2, c->mst, c->stream}) {

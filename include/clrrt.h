@@ -746,6 +746,34 @@ int clrrt_round_sizes(clrrt_ctx* ctx, int64_t* out, int64_t cap, int64_t* n);
  * (the order is a permutation of the round's jobs, length classes do not increase along it, positions ascend within
  * a class), 7 = positions wrong. */
 int clrrt_debug_counters(clrrt_ctx* ctx, int64_t out[64]);
+/* Test facility: guard bands around every device and pinned block this library allocates from now on, in every
+ * context of the process (the exchange library, clrrt_xchg.h, has an owner of its own and stays unguarded).  bytes = G:
+ * 0 (off: the runtime's own pointers, the product path), or a multiple of 256 up to 1 MiB; anything else is
+ * CLRRT_EINVAL.  A block of n bytes then takes n + 2 G from the runtime, both bands hold 0xFF -- a stray read of one
+ * gives NaN or -1 -- and the block starts G bytes in, so its alignment is unchanged.  A block keeps the G it was
+ * allocated with.  Its bands are checked when it is freed (a buffer re-grown or released, clrrt_destroy, an entry
+ * point's scratch at its return), after a device synchronize, and what a free finds is kept for the next
+ * clrrt_debug_mem_check.  An overrun of up to G bytes stays inside the block's own allocation: it is reported and
+ * damages nothing else. */
+int clrrt_debug_mem_guard(int64_t bytes);
+/* Synchronizes the device and checks the bands of every live guarded block, adding what the frees since the last call
+ * found (and forgetting it).  blocks_checked: live blocks + blocks freed since the last call; guard_bytes_checked: 2 G
+ * for each; violations: bands that no longer hold the pattern.  The first of them -- frees in their order, then live
+ * blocks by age --: first_serial, the block's allocation serial number (every allocation of the process through this
+ * library counts from 1, guarded or not, so a later run of the same program finds the site with a host debugger);
+ * first_bytes, its requested size; first_side, -1 the band before the block, +1 the band after it (0: no violation);
+ * first_offset, the first changed byte's offset within that band. */
+typedef struct clrrt_mem_report {
+  int64_t blocks_checked;
+  int64_t guard_bytes_checked;
+  int64_t violations;
+  int64_t first_serial;
+  int64_t first_bytes;
+  int64_t first_offset;
+  int32_t first_side;
+  int32_t reserved;
+} clrrt_mem_report;
+int clrrt_debug_mem_check(clrrt_mem_report* out);
 
 #ifdef __cplusplus
 }

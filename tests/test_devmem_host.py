@@ -1,7 +1,9 @@
 """The owner of a context's device and pinned memory (cl-rrt_amd/csrc/clrrt_devmem.hpp, no HIP) without a GPU: a
 stand-alone host program (its own main, nothing loaded into Python) over counting malloc / free fakes, built with
 -fsanitize=address,undefined.  The fakes' counters say "freed exactly once", the sanitizer's leak check at exit says
-"nothing leaked"."""
+"nothing leaked".  The same program checks the guard bands (clrrt::MemGuard): one changed byte at the first and last byte
+of either band is reported with its side and offset, by a check of the live blocks and at a free; a clean run reports
+nothing; without a guard pointers pass through unchanged; a block keeps the guard it was allocated with."""
 import os
 import subprocess
 

@@ -3814,7 +3814,7 @@ int clrrt_simulate(clrrt_ctx* c, const clrrt_sim_case* cases, int32_t n, clrrt_r
 }
 
 int clrrt_selftest_math(clrrt_ctx* c, int32_t fn, const double* a, const double* b, int32_t n, double* out) {
-  if (!c || n < 0 || (n > 0 && (!a || !b || !out)) || fn < 0 || fn > 28) return CLRRT_EINVAL;
+  if (!c || n < 0 || (n > 0 && (!a || !b || !out)) || fn < 0 || fn > 29) return CLRRT_EINVAL;
   HIPC(c, hipSetDevice(c->device));
   if (n == 0) return CLRRT_OK;
   const char* const pre = "selftest_math: ";

@@ -701,9 +701,10 @@ CLRRT_HD inline __attribute__((always_inline)) double atan2(double y, double x) 
 
 // exp (sysdeps/ieee754/dbl-64/e_exp.c, glibc 2.35, as its FMA ifunc variant __exp_fma evaluates it): x =
 // k ln2/128 + r, exp(x) = 2^(k/128) exp(r) with 2^(k/128) = scale (1 + tail) from __exp_data.tab and a degree-5
-// polynomial; the FMA build contracts the reduction, the polynomial and the final scale + scale * tmp, not the
-// out-of-line specialcase (|x| >= 512).  Checked against the host libm bit for bit on 4e7 arguments
-// (development check) and on the device by tests/test_gpu_math.py.  Used by the W2 obstacle-cost term
+// polynomial; the FMA build contracts the reduction, the polynomial and the final scale + scale * tmp, and of the
+// out-of-line specialcase (|x| >= 512) the overflow side's scale + scale * tmp but not the subnormal side's.
+// Checked against the host libm bit for bit on 4e7 arguments (development check), at its thresholds and table
+// boundaries by tests/test_math_edges_host.py and on the device by tests/test_math_edges_gpu.py.  Used by the W2 obstacle-cost term
 // Wcost[2] exp(-Wcost[3] Dobs) (simulation.cpp:91, rrtplanner.cpp:112).
 #if defined(__HIPCC__)
 static __device__ __constant__ uint64_t d_exp_tab[256] = CLRRT_GLIBC_EXP_TAB;
@@ -726,7 +727,7 @@ CLRRT_HD inline double exp_specialcase(double tmp, uint64_t sbits, uint64_t ki) 
   if ((ki & 0x80000000) == 0) {  // k > 0: the exponent of scale might have overflowed by <= 460
     sbits -= 1009ull << 52;
     scale = from_bits(sbits);
-    y = 0x1p1009 * (scale + scale * tmp);
+    y = 0x1p1009 * fma_(scale, tmp, scale);  // this branch the FMA build does contract (x in [512, 709.78])
     return y;
   }
   // k < 0: the result may be subnormal; avoid double rounding

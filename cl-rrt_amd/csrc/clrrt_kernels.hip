@@ -3074,6 +3074,7 @@ __global__ void k_selftest_math(int fn, const double* __restrict__ a, const doub
     case 21: { double sx, cx; glibc::sincos_sel(x, sx, cx); r = cx; } break;
     case 22: { double sx, cx; glibc::sin_cos_fma_sel(x, sx, cx); r = sx; } break;
     case 23: { double sx, cx; glibc::sin_cos_fma_sel(x, sx, cx); r = cx; } break;
+    case 29: r = (double)glibcf::atanf(xf); break;
     case 18: {  // diagnostics: latency of a rollout step's trig (sincos, cos, sin, tan), y[0] iterations
       double z = x;
       for (int it = 0; it < (int)y; it++) {

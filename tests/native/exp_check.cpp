@@ -26,7 +26,8 @@ int main(int argc, char** argv) {
   for (long i = 0; i < n; i++) {
     s ^= s << 13; s ^= s >> 7; s ^= s << 17;
     double x;
-    if (i % 4 == 0) x = ((s >> 11) * 0x1p-53) * (-760.0) + 10.0;
+    if (i % 8 == 0) x = ((s >> 11) * 0x1p-53) * 720.0;  // incl. [512, 709.78]: specialcase's overflow side
+    else if (i % 4 == 0) x = ((s >> 11) * 0x1p-53) * (-760.0) + 10.0;
     else if (i % 4 == 1) x = -((s >> 11) * 0x1p-53) * 260.0;
     else if (i % 4 == 2) x = ((s >> 11) * 0x1p-53 - 0.5) * 2.0;
     else {

@@ -16,7 +16,7 @@ import clrrt
 pytestmark = pytest.mark.gpu
 
 _libm = C.CDLL("libm.so.6")
-for _n in ("cosf", "sinf", "acosf", "asinf", "sqrtf"):
+for _n in ("cosf", "sinf", "acosf", "asinf", "sqrtf", "atanf"):
     getattr(_libm, _n).restype = C.c_float
     getattr(_libm, _n).argtypes = [C.c_float]
 _libm.sincos.restype = None
@@ -54,13 +54,14 @@ HOST = {
     # the rollout step's branch-free block (glibc::step_trig: x2 = a, x3 = b)
     24: lambda a, b: _sincos(a, 0), 25: lambda a, b: _sincos(a, 1), 26: lambda a, b: math.sin(a),
     27: lambda a, b: math.cos(a), 28: lambda a, b: math.tan(b),
+    29: lambda a, b: float(_libm.atanf(_f32(a))),
 }
 NAMES = ["sin", "cos", "tan", "sqrt", "fmod", "atan2", "exp", "div", "cosf", "sinf", "atan2f", "acosf",
          "asinf", "sqrtf", "fdiv", "round", "sincos.sin", "sincos.cos", None, None, "sincos_sel.sin",
          "sincos_sel.cos", "sin_cos_fma_sel.sin", "sin_cos_fma_sel.cos", "step_trig.s2", "step_trig.c2",
-         "step_trig.swp", "step_trig.cwp", "step_trig.t3"]
-FNS = [f for f in range(29) if f not in (18, 19)]  # 18, 19: latency diagnostics
-EXACT = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 20, 21, 22, 23, 24, 25, 26, 27, 28}
+         "step_trig.swp", "step_trig.cwp", "step_trig.t3", "atanf"]
+FNS = [f for f in range(30) if f not in (18, 19)]  # 18, 19: latency diagnostics
+EXACT = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 20, 21, 22, 23, 24, 25, 26, 27, 28, 29}
 
 
 def _inputs(fn, n, rng):

@@ -104,6 +104,7 @@ _SIGS = {
     "clrrt_tree_rebase": (C.c_int, [C.c_void_p, C.c_int64, P(C.c_double), C.c_double, P(abi.RebaseInfo)]),
     "clrrt_iteration_log": (C.c_int, [C.c_void_p, C.c_int32]),
     "clrrt_exact_stats": (C.c_int, [C.c_void_p, P(C.c_int64)]),
+    "clrrt_exact_fix_hist": (C.c_int, [C.c_void_p, P(C.c_int64)]),
     "clrrt_iteration_records": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, P(abi.Iteration), P(C.c_int64)]),
     "clrrt_obstacle_distance": (C.c_int, [C.c_void_p, P(C.c_double), C.c_int32, P(C.c_double)]),
     "clrrt_debug_counters": (C.c_int, [C.c_void_p, P(C.c_int64)]),
@@ -660,6 +661,17 @@ class Planner:
         # (out[9] is reserved: a window without a result is always resolved, clrrt.h)
         return dict(zip(("rounds", "resolved", "fixup_rollouts", "conflict_rounds", "end_fixup_succeeded", "end_tie",
                          "end_key_eq_thr", "end_over_slots", "end_pushed_out"), list(out)[:9]))
+
+    EXACT_FIX_BUCKETS = ("none", "fix_result", "fix_no_result", "no_result_pushed_out", "tie", "key_eq_thr",
+                         "over_slots", "pushed_out", "recomputed", "recomputed_stood", "recomputed_stopped",
+                         "fixup_succeeded", "tie_cleared")
+
+    def exact_fix_hist(self):
+        """clrrt_exact_fix_hist: the verdicts of the EXACT fix-up logic, per sample of every round's committed prefix
+        and the sample that ended it (the buckets of include/clrrt.h, in EXACT_FIX_BUCKETS order)."""
+        out = (C.c_int64 * 16)()
+        self._chk(self.L.clrrt_exact_fix_hist(self.h, out), "exact_fix_hist")
+        return dict(zip(self.EXACT_FIX_BUCKETS, list(out)[:13]))
 
     def iteration_log(self, on=True):
         self._chk(self.L.clrrt_iteration_log(self.h, 1 if on else 0), "iteration_log")

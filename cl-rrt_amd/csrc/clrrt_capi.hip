@@ -227,7 +227,7 @@ struct clrrt_ctx {
   int exact_fix_cap = 0;
   int* fix_n = nullptr;        // [max_batch]
   int* fix_ids = nullptr;      // [max_batch * FIX_MAX]
-  int* fix_adj = nullptr;      // [max_batch * 5]
+  int* fix_adj = nullptr;      // [max_batch * FIX_ADJ]
   NnRec* fix_xrec = nullptr;   // [2 max_batch] the round's new nodes as nearest-node records
   int* fix_xi = nullptr;       // [2 max_batch] samples whose list is recomputed, their new-node counts
   int* fix_xcand = nullptr;    // [max_batch * K] recomputed lists
@@ -237,7 +237,7 @@ struct clrrt_ctx {
   std::vector<RollRes> h_fix_spec;
   Job* fix_jobs = nullptr;     // [max_batch * CAND_K]
   RollRes* fix_res = nullptr;  // [max_batch * CAND_K]
-  std::vector<int> h_fix;      // fix_n then fix_ids
+  std::vector<int> h_fix;      // fix_n, fix_ids, then fix_adj
   std::vector<clrrt_sample> h_fix_smp;
   std::vector<Job> h_fix_jobs;
   std::vector<int> h_fix_owner;
@@ -247,6 +247,9 @@ struct clrrt_ctx {
   // were not resolved: a fix-up succeeded, tie, key equal to the threshold, > FIX_MAX nodes, k pushed out, full
   // window without a result
   int64_t ex_stats[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  // clrrt_exact_fix_hist: the verdicts of exact_fixups per sample of each round's committed prefix and the sample that
+  // ended it (the buckets of include/clrrt.h), on either side of the recomputed lists' size limit
+  int64_t ex_hist[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   int* roll_perm = nullptr;   // [max_batch * CAND_K] queue order
   int* roll_pflag = nullptr;  // [roll_order_ints(max_batch * CAND_K)] length classes, block histograms, verify marks
   // extractBestPath scratch (allocated on first use, max_nodes entries each)
@@ -1402,6 +1405,12 @@ int clrrt_exact_stats(clrrt_ctx* c, int64_t out[10]) {
   return CLRRT_OK;
 }
 
+int clrrt_exact_fix_hist(clrrt_ctx* c, int64_t out[16]) {
+  if (!c || !out) return CLRRT_EINVAL;
+  for (int i = 0; i < 16; i++) out[i] = c->ex_hist[i];
+  return CLRRT_OK;
+}
+
 int clrrt_iteration_log(clrrt_ctx* c, int32_t on) {
   if (!c) return CLRRT_EINVAL;
   c->iter_log = on != 0;
@@ -2152,7 +2161,7 @@ static int exact_fixups(clrrt_ctx* c, int n, int* L) {
   if (!c->fix_n) {
     HIPC(c, c->mem.renew(&c->fix_n, B));
     HIPC(c, c->mem.renew(&c->fix_ids, B * FIX_MAX));
-    HIPC(c, c->mem.renew(&c->fix_adj, B * 5));
+    HIPC(c, c->mem.renew(&c->fix_adj, B * FIX_ADJ));
     HIPC(c, c->mem.renew(&c->fix_jobs, B * K));
     HIPC(c, c->mem.renew(&c->fix_res, B * K));
     HIPC(c, c->mem.renew(&c->fix_xrec, 2 * B));
@@ -2166,14 +2175,14 @@ static int exact_fixups(clrrt_ctx* c, int n, int* L) {
     HIPC(c, launch_conflict_fix(st, c->dp, n, cur.d_samples, c->regnodes, c->gbnodes, c->so, cur.ctie, cur.ncand, cur.ckey,
                                 c->res_spec, c->fix_n, c->fix_ids, c->fix_adj));
   }
-  c->h_fix.resize((size_t)n * (1 + FIX_MAX + 5));
+  c->h_fix.resize((size_t)n * (1 + FIX_MAX + FIX_ADJ));
   c->h_fix_smp.resize(n);
   c->h_fix_so.resize(n);
   c->h_fix_cand.resize((size_t)n * K);
   c->h_fix_spec.resize((size_t)n * K);
   HIPC(c, hipMemcpyAsync(c->h_fix.data(), c->fix_n, sizeof(int) * n, hipMemcpyDeviceToHost, st));
   HIPC(c, hipMemcpyAsync(c->h_fix.data() + n, c->fix_ids, sizeof(int) * n * FIX_MAX, hipMemcpyDeviceToHost, st));
-  HIPC(c, hipMemcpyAsync(c->h_fix.data() + n * (1 + FIX_MAX), c->fix_adj, sizeof(int) * n * 5, hipMemcpyDeviceToHost,
+  HIPC(c, hipMemcpyAsync(c->h_fix.data() + n * (1 + FIX_MAX), c->fix_adj, sizeof(int) * n * FIX_ADJ, hipMemcpyDeviceToHost,
                          st));
   HIPC(c, hipMemcpyAsync(c->h_fix_smp.data(), cur.d_samples, sizeof(clrrt_sample) * n, hipMemcpyDeviceToHost, st));
   HIPC(c, hipMemcpyAsync(c->h_fix_so.data(), c->so, sizeof(SampleOut) * n, hipMemcpyDeviceToHost, st));
@@ -2199,6 +2208,7 @@ static int exact_fixups(clrrt_ctx* c, int n, int* L) {
   // the samples that need their list recomputed (and whether that fits the LDS kernel)
   const bool x_fits = N + xpre[n] <= nn_exact_small_max() && c->dp.sort_limit <= K;
   int stop = n;
+  int not_found = -1;          // (diagnostics) the sample whose recomputed list no longer holds its result
   std::vector<int> xl;
   for (int j = 0; j < n; j++) {
     if (fn[j] >= 0) continue;
@@ -2255,7 +2265,7 @@ static int exact_fixups(clrrt_ctx* c, int n, int* L) {
         const int id = fid[j * FIX_MAX + i];
         job(j, 1 + (id & 1), id >> 1);
       }
-      const int* ad = fadj + 5 * j;  // old candidates pushed out of the window (samples without a result)
+      const int* ad = fadj + FIX_ADJ * j;  // old candidates pushed out of the window (samples without a result)
       d.rollouts += ad[0]; d.steps += ad[1]; d.f_col += ad[2]; d.f_acc += ad[3]; d.f_it += ad[4];
       continue;
     }
@@ -2292,6 +2302,7 @@ static int exact_fixups(clrrt_ctx* c, int n, int* L) {
     }
     if (o.k >= 0 && !found) {  // the result is not its list's first success any more
       stop = j;
+      not_found = j;
       c->ex_stats[8]++;
       while (!c->h_fix_owner.empty() && c->h_fix_owner.back() == j) {
         c->h_fix_owner.pop_back();
@@ -2344,6 +2355,26 @@ static int exact_fixups(clrrt_ctx* c, int n, int* L) {
     resolved++;
   }
   if (patched) HIPC(c, hipMemcpyAsync(c->so, c->h_fix_so.data(), sizeof(SampleOut) * Lr, hipMemcpyHostToDevice, st));
+  // the verdict histogram: the committed prefix and, where the prefix ends early, the sample that ended it
+  for (int j = 0; j <= Lr && j < n; j++) {
+    int64_t* h = c->ex_hist;
+    const int* ad = fadj + FIX_ADJ * j;
+    if (fn[j] == 0) h[0]++;
+    else if (fn[j] > 0 && c->h_fix_so[j].k >= 0) h[1]++;
+    else if (fn[j] > 0) {
+      h[2]++;
+      h[3] += (ad[0] | ad[1] | ad[2] | ad[3] | ad[4]) != 0;
+    } else if (fn[j] >= -4) {
+      h[3 - fn[j]]++;
+      if (x_fits) {  // (past the size limit such a sample ends the prefix without a recomputed list)
+        h[8]++;
+        h[9] += j < Lr;
+        h[10] += j == not_found;
+      }
+    }
+    h[11] += j == Lr && Lr < stop;
+    h[12] += ad[5] != 0;
+  }
   c->ex_stats[0]++;
   c->ex_stats[1] += resolved;
   c->ex_stats[2] += nj;

@@ -376,8 +376,10 @@ hipError_t launch_nn_exact_x(hipStream_t st, const clrrt_sample* S, const NnRec*
                              const clrrt_node* reg, const clrrt_node* gbn, const SampleOut* so, int n, NnRec* xrec,
                              const int* slist, const int* xcnt, int nlist, int xmax, int* cand, float* ckey,
                              int* ncand, int* ctie);
-// fix_adj[j * 5 ..]: counters (rollouts, steps, collisions, acceleration limits, iteration limits) to add for old
-// candidates of a sample without a result that the grown window pushes out (<= 0)
+// fix_adj[j * FIX_ADJ ..]: counters (rollouts, steps, collisions, acceleration limits, iteration limits) to add for
+// old candidates of a sample without a result that the grown window pushes out (<= 0); then one diagnostic word: the
+// sample's list has equal keys, a node was appended before it, and the unique-key rule let the list stand
+#define FIX_ADJ 6
 hipError_t launch_conflict_fix(hipStream_t st, const DevParams& p, int B, const clrrt_sample* S,
                                const clrrt_node* reg, const clrrt_node* gbn, const SampleOut* so, const int* ctie,
                                const int* ncand, const float* ckey, const RollRes* res, int* fix_n, int* fix_ids,

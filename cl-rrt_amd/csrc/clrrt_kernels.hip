@@ -2267,9 +2267,11 @@ __global__ void k_conflict_fix(DevParams p, int B, const clrrt_sample* __restric
   int ids[FIX_MAX];
   float nk[FIX_MAX];
   int bad = 0;  // why not resolvable: 1 tie, 2 a key equal to the threshold, 3 > FIX_MAX, 4 k pushed out
+  int cleared = 0;  // (diagnostics, clrrt_exact_fix_hist) a tied list met an appended node and stood by the rule above
   for (int k = 0; k < j && !bad; k++) {
     if (so[k].k < 0) continue;
     if (tie) { bad = 1; break; }
+    cleared = ctie[j] != 0;
     for (int w = 0; w < 2; w++) {
       if (w == 1 && !so[k].gb_ok) break;
       const clrrt_node& n = w == 0 ? regnodes[k] : gbnodes[k];
@@ -2326,7 +2328,8 @@ __global__ void k_conflict_fix(DevParams p, int B, const clrrt_sample* __restric
   }
   for (int a = 0; a < (bad ? 0 : mw); a++) fix_ids[j * FIX_MAX + a] = ids[a];
 #pragma unroll
-  for (int q = 0; q < 5; q++) fix_adj[j * 5 + q] = adj[q];
+  for (int q = 0; q < 5; q++) fix_adj[j * FIX_ADJ + q] = adj[q];
+  fix_adj[j * FIX_ADJ + 5] = cleared;
   fix_n[j] = bad ? -bad : mw;
 }
 

@@ -367,6 +367,24 @@ typedef struct clrrt_iteration {
  * out[8] the accepted candidate pushed out of the sortLimit window; out[9] reserved (0: a window without a result
  * is always resolved by ranking the new nodes into it). */
 int clrrt_exact_stats(clrrt_ctx* ctx, int64_t out[10]);
+/* Read-only diagnostic beside clrrt_exact_stats: how the EXACT rounds with fix-ups (option "exact_fixup") decided
+ * their samples since the context was made.  Counted on the host, once per round, over the round's committed prefix
+ * and (where the prefix ends early) the sample that ended it, whether or not the tree is past the size up to which an
+ * unresolved sample gets its list recomputed:
+ *   out[0]  no appended node enters the sample's list before its result (nothing to do)
+ *   out[1]  m > 0 such nodes, the sample has a result: m fix-up rollouts
+ *   out[2]  m > 0 such nodes inside the window of a sample without a result
+ *   out[3]  of out[2], samples whose grown window pushed out old candidates (their counters are subtracted)
+ *   out[4]  unresolved: equal keys in the sample's list          out[5]  a new key equal to the sample's threshold
+ *   out[6]  unresolved: more new nodes than fix-up slots         out[7]  the result pushed out of the sortLimit window
+ *   out[8]  unresolved samples whose list was recomputed over the tree and the round's new nodes
+ *   out[9]  of out[8], samples that were committed with the recomputed list
+ *   out[10] of out[8], samples whose result is not the recomputed list's first success (the prefix ends)
+ *   out[11] prefixes ended by a fix-up rollout that succeeded (or, under "exact_fixup_cap", reached the cap)
+ *   out[12] samples with equal keys in their list, after an appended node, that stood because the result's key is
+ *           unique in the list and not the window's last entry
+ * out[13..15] are 0 (reserved). */
+int clrrt_exact_fix_hist(clrrt_ctx* ctx, int64_t out[16]);
 /* on != 0: start (or restart) logging, clearing the records; 0: stop and clear. */
 int clrrt_iteration_log(clrrt_ctx* ctx, int32_t on);
 /* Records logged so far (*n_total), and records [first, first + count) into out. */

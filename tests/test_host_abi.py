@@ -27,6 +27,24 @@ def test_library_loads_and_exports_every_header_symbol():
     assert set(clrrt.exported_symbols()) <= set(declared)
 
 
+def test_exact_fix_hist_is_an_additive_entry():
+    """clrrt_exact_fix_hist (the EXACT fix-up verdict histogram) joins the C-ABI beside clrrt_exact_stats: declared in
+    the header with 16 int64 slots, exported, bound by the Python wrapper with one name per documented bucket, and
+    rejecting null arguments -- with the ABI version left as it is."""
+    import ctypes as C
+    txt = open(clrrt.HEADER_PATH).read()
+    assert re.search(r"int\s+clrrt_exact_fix_hist\(clrrt_ctx\*\s*ctx,\s*int64_t\s+out\[16\]\);", txt)
+    assert re.search(r"int\s+clrrt_exact_stats\(clrrt_ctx\*\s*ctx,\s*int64_t\s+out\[10\]\);", txt)
+    assert "clrrt_exact_fix_hist" in clrrt.exported_symbols()
+    assert len(clrrt.Planner.EXACT_FIX_BUCKETS) == 13 == len(set(clrrt.Planner.EXACT_FIX_BUCKETS))
+    for k in range(13):
+        assert re.search(r"out\[%d\]" % k, txt[txt.index("Read-only diagnostic beside clrrt_exact_stats"):
+                                               txt.index("int clrrt_exact_fix_hist")])
+    L = clrrt.lib()
+    out = (C.c_int64 * 16)()
+    assert L.clrrt_exact_fix_hist(None, out) == -1 and L.clrrt_abi_version() == 11
+
+
 def test_abi_record_sizes_match_header():
     import ctypes as C
     assert C.sizeof(abi.Node) == 160

@@ -42,6 +42,10 @@ _SIGS = {
     "clrrt_set_obstacles": (C.c_int, [C.c_void_p, P(abi.Obstacle), C.c_int32]),
     "clrrt_set_occupancy": (C.c_int, [C.c_void_p, P(abi.Occupancy), C.c_void_p]),
     "clrrt_occupancy_info": (C.c_int, [C.c_void_p, P(abi.OccupancyInfo)]),
+    "clrrt_set_occupancy_layers": (C.c_int, [C.c_void_p, P(abi.Occupancy), C.c_int32, C.c_double, C.c_double,
+                                             C.c_void_p]),
+    "clrrt_occupancy_layers_info": (C.c_int, [C.c_void_p, P(abi.OccupancyLayersInfo)]),
+    "clrrt_occupancy_field_layer": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
     "clrrt_set_occupancy_clearance": (C.c_int, [C.c_void_p, C.c_double]),
     "clrrt_occupancy_clearance_info": (C.c_int, [C.c_void_p, P(abi.ClearanceInfo)]),
     "clrrt_occupancy_field": (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -288,6 +292,28 @@ class Planner:
         o = abi.Occupancy(x0, y0, res, inflate, cells.shape[1], cells.shape[0])
         self._chk(self.L.clrrt_set_occupancy(self.h, C.byref(o), C.c_void_p(cells.ctypes.data)), "set_occupancy")
 
+    def set_occupancy_layers(self, x0, y0, res, cells3d, t0, dt, inflate=None):
+        """A stack of time layers (clrrt_set_occupancy_layers): cells3d[k, j, i] != 0 marks cell (i, j) of layer k,
+        which serves the rollout times t0 + k dt <= t < t0 + (k + 1) dt (layer 0 every earlier time too, the last
+        layer every later one); geometry and inflate as in set_occupancy.  cells3d None clears."""
+        if cells3d is None:
+            self._chk(self.L.clrrt_set_occupancy_layers(self.h, None, 0, 0.0, 0.0, None), "set_occupancy_layers")
+            return
+        cells = np.ascontiguousarray(np.asarray(cells3d) != 0, dtype=np.uint8)
+        if cells.ndim != 3:
+            raise ValueError("cells3d must be a 3D array [layers, h, w]")
+        inflate = res * np.sqrt(2.0) / 2.0 if inflate is None else inflate
+        o = abi.Occupancy(x0, y0, res, inflate, cells.shape[2], cells.shape[1])
+        self._chk(self.L.clrrt_set_occupancy_layers(self.h, C.byref(o), cells.shape[0], float(t0), float(dt),
+                                                    C.c_void_p(cells.ctypes.data)), "set_occupancy_layers")
+
+    def occupancy_layers_info(self):
+        o = abi.OccupancyLayersInfo()
+        self._chk(self.L.clrrt_occupancy_layers_info(self.h, C.byref(o)), "occupancy_layers_info")
+        d = {k: getattr(o, k) for k, _ in abi.OccupancyLayersInfo._fields_}
+        d["occupied"] = [int(v) for v in o.occupied]
+        return d
+
     def occupancy_info(self):
         o = abi.OccupancyInfo()
         self._chk(self.L.clrrt_occupancy_info(self.h, C.byref(o)), "occupancy_info")
@@ -304,11 +330,12 @@ class Planner:
         self._chk(self.L.clrrt_occupancy_clearance_info(self.h, C.byref(o)), "occupancy_clearance_info")
         return {k: getattr(o, k) for k, _ in abi.ClearanceInfo._fields_}
 
-    def occupancy_field(self):
-        """The baked squared distance field, uint32 [h, w] (0xFFFFFFFF: no occupied cell)."""
+    def occupancy_field(self, layer=0):
+        """The baked squared distance field of a layer, uint32 [h, w] (0xFFFFFFFF: no occupied cell)."""
         i = self.occupancy_info()
         out = np.empty((max(i["h"], 1), max(i["w"], 1)), dtype=np.uint32)
-        self._chk(self.L.clrrt_occupancy_field(self.h, C.c_void_p(out.ctypes.data)), "occupancy_field")
+        self._chk(self.L.clrrt_occupancy_field_layer(self.h, int(layer), C.c_void_p(out.ctypes.data)),
+                  "occupancy_field")
         return out
 
     def occupancy_clearance(self, states):

@@ -16,7 +16,8 @@ CLRRT_MODE_BATCH = 1
 CLRRT_COLLISION_STUB = 0
 CLRRT_COLLISION_OBB = 1
 CLRRT_COLLISION_OCC = 2  # the static occupancy grid (clrrt_set_occupancy), then the OBB test
-OCC_NONE, OCC_LDS, OCC_GLOBAL = 0, 1, 2  # CLRRT_OCC_*: where the rollout kernels hold the grid's bitmaps
+OCC_NONE, OCC_LDS, OCC_GLOBAL, OCC_REACH_LDS = 0, 1, 2, 3  # CLRRT_OCC_*: where the rollout kernels hold the grid's bitmaps
+OCC_MAX_LAYERS = 16  # CLRRT_OCC_MAX_LAYERS
 
 ROLL_ITERLIMIT, ROLL_END, ROLL_GOAL, ROLL_COLLISION, ROLL_ACCLIMIT = range(5)
 ROLL_NAMES = {ROLL_ITERLIMIT: "iterlimit", ROLL_END: "end", ROLL_GOAL: "goal",
@@ -59,6 +60,12 @@ class OccupancyInfo(C.Structure):  # clrrt_occupancy_info_t
     _fields_ = [("w", C.c_int32), ("h", C.c_int32), ("reach_w", C.c_int32), ("reach_h", C.c_int32),
                 ("reach_k", C.c_int32), ("placement", C.c_int32), ("occupied", C.c_int64),
                 ("map_bytes", C.c_int64), ("bake_ms", C.c_double)]
+
+
+class OccupancyLayersInfo(C.Structure):  # clrrt_occupancy_layers_info_t
+    _fields_ = [("layers", C.c_int32), ("placement", C.c_int32), ("t0", C.c_double), ("dt", C.c_double),
+                ("occupied", C.c_int64 * OCC_MAX_LAYERS), ("map_bytes", C.c_int64),
+                ("union_reach_bytes", C.c_int64), ("field_bytes", C.c_int64), ("bake_ms", C.c_double)]
 
 
 class ClearanceInfo(C.Structure):  # clrrt_clearance_info_t
@@ -150,6 +157,7 @@ def _check_sizes():
     assert C.sizeof(ExchangeIO) == 128, C.sizeof(ExchangeIO)
     assert C.sizeof(Occupancy) == 40 and C.sizeof(OccupancyInfo) == 48
     assert C.sizeof(ClearanceInfo) == 32
+    assert C.sizeof(OccupancyLayersInfo) == 184
     assert C.sizeof(RebaseInfo) == 64
 
 

@@ -62,3 +62,29 @@ def rasterize(obstacles, x0, y0, res, w, h):
         v = dy * c - dx * s
         out |= (np.abs(u) <= sy / 4.0) & (np.abs(v) <= sx / 4.0)
     return out.astype(np.uint8)
+
+
+def rasterize_layers(obstacles, x0, y0, res, w, h, layers, t0, dt, sub=4):
+    """A stack of occupancy cells (uint8 [layers, h, w]) for set_occupancy_layers: layer k is rasterize's static cells
+    plus every moving box at the times t = t0 + (k + s / sub) dt, s = 0 .. sub, of its slice -- centre + (vx, vy) t,
+    heading fixed, as the OBB path predicts it -- rasterised the same way and united.  A scene generator for tests
+    and tools, NOT a conservative sweep: a cell the box only crosses between two of the sampled times stays free."""
+    obs = np.asarray(obstacles, dtype=np.float64).reshape(-1, 7)
+    static = rasterize(obs, x0, y0, res, w, h).astype(bool)
+    cx = x0 + (np.arange(w) + 0.5) * res
+    cy = y0 + (np.arange(h) + 0.5) * res
+    X, Y = np.meshgrid(cx, cy)
+    out = np.zeros((layers, h, w), dtype=bool)
+    for k in range(layers):
+        out[k] = static
+        for ox, oy, th, sx, sy, vx, vy in obs:
+            if vx == 0.0 and vy == 0.0:
+                continue
+            c, sn = np.cos(th), np.sin(th)
+            for s in range(sub + 1):
+                t = t0 + (k + s / sub) * dt
+                dx, dy = X - (ox + vx * t), Y - (oy + vy * t)
+                u = dx * c + dy * sn
+                v = dy * c - dx * sn
+                out[k] |= (np.abs(u) <= sy / 4.0) & (np.abs(v) <= sx / 4.0)
+    return out.astype(np.uint8)

@@ -110,11 +110,13 @@ struct clrrt_ctx {
   size_t grid_bytes = 0;
   int grid_exempt = 0;         // obstacles exempt from culling (always-tested list, see build_grid)
   // the static occupancy grid (CLRRT_COLLISION_OCC, clrrt_set_occupancy): the baked maps' device view (w == 0:
-  // none), their buffer (cell bytes | count | occ words | reach words), the occupied count and the bake's events
+  // none), their buffer (cell bytes | counts | occ words | reach words | union reach words, each but the counts once
+  // per layer of a stack), the occupied count (all layers, and per layer) and the bake's events
   OccGrid occ{};
   void* occ_buf = nullptr;
   size_t occ_bytes = 0;
   int64_t occ_count = 0;
+  int64_t occ_counts[CLRRT_OCC_MAX_LAYERS] = {};
   hipEvent_t occ_ev[2] = {nullptr, nullptr};
   float occ_bake_ms = 0.f;
   // the occupancy clearance (clrrt_set_occupancy_clearance): its cap (0: off), the field's buffer (field dwords | row
@@ -1002,9 +1004,9 @@ static int bake_field(clrrt_ctx* c) {
   g.field = nullptr;
   g.clear_max = 0.0;
   c->clr_bake_ms = 0.f;
-  const size_t ncell = (size_t)g.w * g.h;
+  const size_t ncell = (size_t)g.w * g.h * g.layers;  // (layer k's field: w h dwords behind layer k - 1's)
   const size_t field_b = (sizeof(uint32_t) * ncell + 255) / 256 * 256, rowd_b = (sizeof(uint16_t) * ncell + 255) / 256 * 256;
-  const size_t need = field_b + rowd_b + 64 * sizeof(uint32_t);
+  const size_t need = field_b + rowd_b + 64 * sizeof(uint32_t) * g.layers;
   if (need > c->clr_bytes) {
     c->clr_bytes = 0;
     HIPC(c, c->mem.renew_bytes(&c->clr_buf, need));
@@ -1019,11 +1021,14 @@ static int bake_field(clrrt_ctx* c) {
   HIPC(c, hipStreamSynchronize(c->stream));
   HIPC(c, hipEventElapsedTime(&c->clr_bake_ms, c->clr_ev[0], c->clr_ev[1]));
   g.field = (const uint32_t*)b;
+  g.field_stride = g.w * g.h;
   g.clear_max = c->clr_max;
   return CLRRT_OK;
 }
 
-int clrrt_set_occupancy(clrrt_ctx* c, const clrrt_occupancy* o, const uint8_t* cells) {
+// clrrt_set_occupancy (one layer) and clrrt_set_occupancy_layers: `fn` names the call in the error texts.
+static int set_occ_stack(clrrt_ctx* c, const clrrt_occupancy* o, int32_t layers, double t0, double dt,
+                         const uint8_t* cells, const std::string& fn) {
   if (!c) return CLRRT_EINVAL;
   HIPC(c, hipSetDevice(c->device));
   if (!o || o->w == 0) {  // clear
@@ -1031,25 +1036,32 @@ int clrrt_set_occupancy(clrrt_ctx* c, const clrrt_occupancy* o, const uint8_t* c
     if (frc != CLRRT_OK) return frc;
     c->occ = OccGrid{};
     c->occ_count = 0;
+    for (auto& n : c->occ_counts) n = 0;
     c->occ_bake_ms = 0.f;
     return CLRRT_OK;
   }
-  if (o->w < 0 || o->w > 2048) return fail(c, CLRRT_EINVAL, "set_occupancy: w outside [0, 2048]");
-  if (o->h < 1 || o->h > 2048) return fail(c, CLRRT_EINVAL, "set_occupancy: h outside [1, 2048]");
-  if ((int64_t)o->w * o->h > ((int64_t)1 << 22)) return fail(c, CLRRT_EINVAL, "set_occupancy: w * h above 2^22");
-  if (!std::isfinite(o->x0)) return fail(c, CLRRT_EINVAL, "set_occupancy: x0 is not finite");
-  if (!std::isfinite(o->y0)) return fail(c, CLRRT_EINVAL, "set_occupancy: y0 is not finite");
-  if (!(std::isfinite(o->res) && o->res > 0.0)) return fail(c, CLRRT_EINVAL, "set_occupancy: res is not finite and > 0");
+  if (layers < 1 || layers > CLRRT_OCC_MAX_LAYERS)
+    return fail(c, CLRRT_EINVAL, fn + ": layers outside [1, " + std::to_string(CLRRT_OCC_MAX_LAYERS) + "]");
+  if (o->w < 0 || o->w > 2048) return fail(c, CLRRT_EINVAL, fn + ": w outside [0, 2048]");
+  if (o->h < 1 || o->h > 2048) return fail(c, CLRRT_EINVAL, fn + ": h outside [1, 2048]");
+  if ((int64_t)o->w * o->h > ((int64_t)1 << 22)) return fail(c, CLRRT_EINVAL, fn + ": w * h above 2^22");
+  if ((int64_t)o->w * o->h * layers > ((int64_t)1 << 24))
+    return fail(c, CLRRT_EINVAL, fn + ": w * h * layers above 2^24");
+  if (!std::isfinite(t0)) return fail(c, CLRRT_EINVAL, fn + ": t0 is not finite");
+  if (!(std::isfinite(dt) && dt > 0.0)) return fail(c, CLRRT_EINVAL, fn + ": dt is not finite and > 0");
+  if (!std::isfinite(o->x0)) return fail(c, CLRRT_EINVAL, fn + ": x0 is not finite");
+  if (!std::isfinite(o->y0)) return fail(c, CLRRT_EINVAL, fn + ": y0 is not finite");
+  if (!(std::isfinite(o->res) && o->res > 0.0)) return fail(c, CLRRT_EINVAL, fn + ": res is not finite and > 0");
   if (!(std::isfinite(o->inflate) && o->inflate >= 0.0 && o->inflate <= 1000.0))
-    return fail(c, CLRRT_EINVAL, "set_occupancy: inflate is not finite and within [0, 1000]");
-  if (!cells) return fail(c, CLRRT_EINVAL, "set_occupancy: cells is NULL");
+    return fail(c, CLRRT_EINVAL, fn + ": inflate is not finite and within [0, 1000]");
+  if (!cells) return fail(c, CLRRT_EINVAL, fn + ": cells is NULL");
   // the reach map (clrrt_occ.hpp): cells of rk x rk occupancy cells, about max(0.5 m, R / 8) wide, rm of them around
   // the grid; Rc: the reach radius plus the rounding slack, in occupancy cells
   const double R = std::sqrt(2.424 * 2.424 + 1.0) + o->inflate * std::sqrt(2.0);
   const double ext = std::max(o->w, o->h) * o->res + 2.0 * R;
   const double mag = std::fabs(o->x0) + std::fabs(o->y0) + ext;
   if (!(o->res >= mag * (1.0 / 1073741824.0)))
-    return fail(c, CLRRT_EINVAL, "set_occupancy: res is below 2^-30 of the grid's coordinates");
+    return fail(c, CLRRT_EINVAL, fn + ": res is below 2^-30 of the grid's coordinates");
   OccGrid g{};
   g.x0 = o->x0; g.y0 = o->y0; g.res = o->res; g.inflate = o->inflate;
   g.w = o->w; g.h = o->h;
@@ -1063,10 +1075,16 @@ int clrrt_set_occupancy(clrrt_ctx* c, const clrrt_occupancy* o, const uint8_t* c
   g.rres = g.rk * o->res;
   g.rx0 = o->x0 - g.rm * g.rres;
   g.ry0 = o->y0 - g.rm * g.rres;
-  const size_t ncell = (size_t)o->w * o->h;
+  g.layers = layers;
+  g.t0 = t0; g.dt = dt;
+  g.occ_stride = g.h * g.ws;
+  g.reach_stride = g.rh * g.rws;
+  const size_t ncell = (size_t)o->w * o->h * layers;
   const size_t cell_b = (ncell + 255) / 256 * 256;
-  const size_t occ_b = sizeof(uint32_t) * (size_t)g.h * g.ws, reach_b = sizeof(uint32_t) * (size_t)g.rh * g.rws;
-  const size_t need = cell_b + 256 + occ_b + reach_b;
+  const size_t occ_b = sizeof(uint32_t) * (size_t)g.occ_stride * layers;
+  const size_t reach_b = sizeof(uint32_t) * (size_t)g.reach_stride * layers;
+  const size_t union_b = layers > 1 ? sizeof(uint32_t) * (size_t)g.reach_stride : 0;
+  const size_t need = cell_b + 256 + occ_b + reach_b + union_b;
   const int frc = flush_replays(c);  // pending replays collide against the scene they were committed with
   if (frc != CLRRT_OK) return frc;
   HIPC(c, hipStreamSynchronize(c->stream));  // (no launch still reads the old maps)
@@ -1082,21 +1100,33 @@ int clrrt_set_occupancy(clrrt_ctx* c, const clrrt_occupancy* o, const uint8_t* c
   unsigned int* d_count = (unsigned int*)(d_cells + cell_b);
   g.occ = (const uint32_t*)(d_cells + cell_b + 256);
   g.reach = (const uint32_t*)(d_cells + cell_b + 256 + occ_b);
+  g.reach_u = layers > 1 ? (const uint32_t*)(d_cells + cell_b + 256 + occ_b + reach_b) : g.reach;
   c->occ = OccGrid{};  // (a failure below leaves no grid)
-  unsigned int count = 0;
+  unsigned int count[CLRRT_OCC_MAX_LAYERS] = {};
   HIPC(c, hipEventRecord(c->occ_ev[0], c->stream));
   HIPC(c, hipMemcpyAsync(d_cells, cells, ncell, hipMemcpyHostToDevice, c->stream));
-  HIPC(c, hipMemsetAsync(d_count, 0, sizeof(unsigned int), c->stream));
+  HIPC(c, hipMemsetAsync(d_count, 0, sizeof(count), c->stream));
   HIPC(c, launch_occ_bake(c->stream, d_cells, g, Rc, d_count));
   HIPC(c, hipEventRecord(c->occ_ev[1], c->stream));
-  HIPC(c, hipMemcpyAsync(&count, d_count, sizeof(count), hipMemcpyDeviceToHost, c->stream));
+  HIPC(c, hipMemcpyAsync(count, d_count, sizeof(count), hipMemcpyDeviceToHost, c->stream));
   HIPC(c, hipStreamSynchronize(c->stream));
   HIPC(c, hipEventElapsedTime(&c->occ_bake_ms, c->occ_ev[0], c->occ_ev[1]));
   c->occ = g;
-  c->occ_count = count;
+  c->occ_count = 0;
+  for (int k = 0; k < CLRRT_OCC_MAX_LAYERS; k++) c->occ_count += c->occ_counts[k] = count[k];
   if (c->clr_max > 0.0) return bake_field(c);
   return CLRRT_OK;
 }
+
+int clrrt_set_occupancy(clrrt_ctx* c, const clrrt_occupancy* o, const uint8_t* cells) {
+  return set_occ_stack(c, o, 1, 0.0, 1.0, cells, "set_occupancy");
+}
+
+int clrrt_set_occupancy_layers(clrrt_ctx* c, const clrrt_occupancy* o, int32_t layers, double t0, double dt,
+                               const uint8_t* cells) {
+  return set_occ_stack(c, o, layers, t0, dt, cells, "set_occupancy_layers");
+}
+
 
 int clrrt_set_occupancy_clearance(clrrt_ctx* c, double clear_max) {
   if (!c) return CLRRT_EINVAL;
@@ -1126,19 +1156,24 @@ int clrrt_occupancy_clearance_info(clrrt_ctx* c, clrrt_clearance_info_t* out) {
   out->clear_max = c->clr_max;
   out->on = c->clr_max > 0.0;
   out->baked = c->occ.field != nullptr;
-  out->field_bytes = out->baked ? (int64_t)sizeof(uint32_t) * c->occ.w * c->occ.h : 0;
+  out->field_bytes = out->baked ? (int64_t)sizeof(uint32_t) * c->occ.w * c->occ.h * c->occ.layers : 0;
   out->bake_ms = c->clr_bake_ms;
   return CLRRT_OK;
 }
 
-int clrrt_occupancy_field(clrrt_ctx* c, uint32_t* out) {
+int clrrt_occupancy_field_layer(clrrt_ctx* c, int32_t layer, uint32_t* out) {
   if (!c || !out) return CLRRT_EINVAL;
   if (!c->occ.field) return fail(c, CLRRT_ESTATE, "occupancy_field: no field is baked (clrrt_set_occupancy_clearance with a grid set)");
+  if (layer < 0 || layer >= c->occ.layers)
+    return fail(c, CLRRT_EINVAL, "occupancy_field_layer: layer outside [0, " + std::to_string(c->occ.layers) + ")");
   HIPC(c, hipSetDevice(c->device));
-  HIPC(c, hipMemcpyAsync(out, c->occ.field, sizeof(uint32_t) * (size_t)c->occ.w * c->occ.h, hipMemcpyDeviceToHost, c->stream));
+  HIPC(c, hipMemcpyAsync(out, c->occ.field + (size_t)layer * c->occ.field_stride,
+                         sizeof(uint32_t) * (size_t)c->occ.w * c->occ.h, hipMemcpyDeviceToHost, c->stream));
   HIPC(c, hipStreamSynchronize(c->stream));
   return CLRRT_OK;
 }
+
+int clrrt_occupancy_field(clrrt_ctx* c, uint32_t* out) { return clrrt_occupancy_field_layer(c, 0, out); }
 
 int clrrt_occupancy_clearance(clrrt_ctx* c, const double* states, int32_t n, double* out) {
   if (!c || n < 0 || (n > 0 && (!states || !out))) return CLRRT_EINVAL;
@@ -1150,10 +1185,19 @@ int clrrt_occupancy_clearance(clrrt_ctx* c, const double* states, int32_t n, dou
   HIPP(c, pre, din.alloc(10 * (size_t)n));
   HIPP(c, pre, dout.alloc(n));
   HIPP(c, pre, hipMemcpyAsync(din, states, sizeof(double) * 10 * (size_t)n, hipMemcpyHostToDevice, c->stream));
-  HIPP(c, pre, launch_occ_clearance(c->stream, c->occ, din, n, dout));
+  HIPP(c, pre, launch_occ_clearance(c->stream, c->occ, c->params.obs_use_pred, din, n, dout));
   HIPP(c, pre, hipMemcpyAsync(out, dout, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
   HIPP(c, pre, hipStreamSynchronize(c->stream));
   return CLRRT_OK;
+}
+
+// CLRRT_OCC_* of a k_roll_run launch of `a` (the grid in a.occ).
+static int occ_placement(const RollArgs& a) {
+  switch (roll_occ_placement(a)) {
+    case OCC_IN_LDS: return CLRRT_OCC_LDS;
+    case OCC_IN_LDS_UNION: return CLRRT_OCC_REACH_LDS;
+    default: return CLRRT_OCC_GLOBAL;
+  }
 }
 
 int clrrt_occupancy_info(clrrt_ctx* c, clrrt_occupancy_info_t* out) {
@@ -1166,9 +1210,29 @@ int clrrt_occupancy_info(clrrt_ctx* c, clrrt_occupancy_info_t* out) {
   RollArgs a = roll_args(c, 0);
   a.occ = g;  // (the placement a mode-2 launch takes, whichever mode is set now)
   a.coop_enable = c->roll_coop;
-  out->placement = roll_occ_in_lds(a) ? CLRRT_OCC_LDS : CLRRT_OCC_GLOBAL;
+  out->placement = occ_placement(a);
   out->occupied = c->occ_count;
   out->map_bytes = (int64_t)occ_map_bytes(g);
+  out->bake_ms = c->occ_bake_ms;
+  return CLRRT_OK;
+}
+
+int clrrt_occupancy_layers_info(clrrt_ctx* c, clrrt_occupancy_layers_info_t* out) {
+  if (!c || !out) return CLRRT_EINVAL;
+  memset(out, 0, sizeof(*out));
+  const OccGrid& g = c->occ;
+  if (g.w <= 0) return CLRRT_OK;
+  RollArgs a = roll_args(c, 0);
+  a.occ = g;
+  a.coop_enable = c->roll_coop;
+  out->layers = g.layers;
+  out->placement = occ_placement(a);
+  out->t0 = g.t0;
+  out->dt = g.dt;
+  for (int k = 0; k < CLRRT_OCC_MAX_LAYERS; k++) out->occupied[k] = c->occ_counts[k];
+  out->map_bytes = (int64_t)occ_map_bytes(g);
+  out->union_reach_bytes = g.layers > 1 ? (int64_t)occ_union_bytes(g) : 0;
+  out->field_bytes = g.field ? (int64_t)sizeof(uint32_t) * g.w * g.h * g.layers : 0;
   out->bake_ms = c->occ_bake_ms;
   return CLRRT_OK;
 }

@@ -97,6 +97,14 @@ struct ObsGrid {
 // no grid (the mode-1 instantiations run).  in_lds / lds_off: set per launch (occ_place).  field: the squared
 // distance field of clrrt_set_occupancy_clearance (w x h dwords, global memory; null: clearance off or not baked),
 // clear_max its cap.
+// A stack (clrrt_set_occupancy_layers) holds `layers` such grids of one geometry: layer k's maps start k occ_stride /
+// k reach_stride words behind occ / reach and its field k field_stride dwords behind field; a state's layer is
+// occ_layer(g, t) of its step's time (t0, dt: the first slice's start and the slices' length).  reach_u: the bitwise
+// OR of the layers' reach maps (a stack of one layer: its reach map).  in_lds: OCC_IN_GLOBAL, OCC_IN_LDS (all layers'
+// two bitmaps, laid out as in global memory) or OCC_IN_LDS_UNION (reach_u alone).
+#define OCC_IN_GLOBAL 0
+#define OCC_IN_LDS 1
+#define OCC_IN_LDS_UNION 2
 struct OccGrid {
   const uint32_t* occ;
   const uint32_t* reach;
@@ -107,6 +115,10 @@ struct OccGrid {
   int w, h, ws;
   int rw, rh, rws, rk, rm;
   int in_lds, lds_off;
+  int layers;
+  int occ_stride, reach_stride, field_stride;
+  double t0, dt;
+  const uint32_t* reach_u;
 };
 
 struct RollArgs {
@@ -415,17 +427,18 @@ hipError_t launch_append(hipStream_t st, const clrrt_node* in, int n, int64_t ba
 hipError_t launch_selftest_math(hipStream_t st, int fn, const double* a, const double* b, int n, double* out);
 hipError_t launch_obs_distance(hipStream_t st, const DevParams& p, const BakedObs* obs, const double* states, int n,
                                double* out, const OccGrid* occ = nullptr);
-// clrrt_set_occupancy's bake: the cell bytes into g.occ, then g.reach from it; Rc = the reach radius in cells
-// (clrrt_occ.hpp), *count += occupied cells.
+// The occupancy bake: every layer's cell bytes into g.occ, then g.reach from it and, for a stack, g.reach_u from that;
+// Rc = the reach radius in cells (clrrt_occ.hpp), count[k] += occupied cells of layer k.
 hipError_t launch_occ_bake(hipStream_t st, const uint8_t* cells, const OccGrid& g, double Rc, unsigned int* count);
 // clrrt_set_occupancy_clearance's bake (clrrt_occ.hpp): the squared distance field of g.occ into field (w h dwords),
 // through the row distances rowd (w h halfwords) and the non-empty-row mask rowmask (64 words, zeroed here).
 hipError_t launch_occ_field(hipStream_t st, const OccGrid& g, uint16_t* rowd, uint32_t* rowmask, uint32_t* field);
 // Clearance of n states (10 doubles each) against g.field, by the step loops' device function.
-hipError_t launch_occ_clearance(hipStream_t st, const OccGrid& g, const double* states, int n, double* out);
+hipError_t launch_occ_clearance(hipStream_t st, const OccGrid& g, int use_pred, const double* states, int n, double* out);
 // Bytes of the two maps, and whether the persistent rollout launch of these arguments holds them in LDS.
 size_t occ_map_bytes(const OccGrid& g);
-bool roll_occ_in_lds(const RollArgs& a);
+int roll_occ_placement(const RollArgs& a);  // OCC_IN_* of a k_roll_run launch of these arguments
+size_t occ_union_bytes(const OccGrid& g);
 // Whether launch_rollout_persistent runs the wave-cooperative collision check (k_roll_run<_, true, _>) for these
 // arguments: option roll_coop, OBB collision without the gap value, a static grid, and LDS room for the scratch.
 bool roll_coop_applies(const RollArgs& a);

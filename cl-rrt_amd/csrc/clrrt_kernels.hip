@@ -1018,25 +1018,35 @@ __device__ __forceinline__ int roll_step_post(Roll& r, const DevParams& p, doubl
 }
 
 // CLRRT_COLLISION_OCC (the OCC instantiations): the static occupancy grid first -- a hit is Dobs = 0 with no box test
-// made or counted -- then the obstacle list as mode 1 has it.
-template <bool NEED_GAP>
+// made or counted -- then the obstacle list as mode 1 has it.  roll_occ_layer: the layer of the step's time, the very
+// value obs_distance gives the moving boxes.
+// value obs_distance gives the moving boxes, computed once per step (k) for the hit test and the clearance.
+// The rollout kernels' OCC parameter: 0 no grid, 1 a single grid -- the code it had before stacks existed --, 2 a
+// stack of more than one layer (LAYERED below); the launch wrappers pick it by OccGrid::layers.  The one-launch
+// kernels (re-init, rebase check, the hooks) have one OCC instantiation, which is the layered one.
+__device__ __forceinline__ int roll_occ_layer(const Roll& r, const DevParams& p, const OccView& oc) {
+  return occ_layer(*oc.g, p.obs_use_pred ? r.x6 : 0.0);
+}
+template <bool NEED_GAP, bool LAYERED = true>
 __device__ __forceinline__ double obs_distance_occ(const Roll& r, const DevParams& p, const ObsView& ov, OccView& oc,
-                                                   uint32_t& tests) {
-  if (occ_hit(oc, r.x0 + 1.424 * r.c2, r.x1 + 1.424 * r.s2, r.x2, r.c2, r.s2)) return 0.0;
+                                                   uint32_t& tests, int k) {
+  if (occ_hit<LAYERED>(oc, k, r.x0 + 1.424 * r.c2, r.x1 + 1.424 * r.s2, r.x2, r.c2, r.s2)) return 0.0;
   return obs_distance<NEED_GAP>(r, p, ov, tests);
 }
 
-template <bool NEED_GAP, bool OCC = false>
+template <bool NEED_GAP, int OCC = 0>
 __device__ __forceinline__ int roll_step(Roll& r, const DevParams& p, const ObsView& ov, OccView& oc, double& col7,
                                          double& col8, double& col9, WorkCtr& w, PhaseClk* pc = nullptr) {
   const double d2 = roll_step_pre(r, p, col7, col8, col9, w, pc);
   // collision (simulation.cpp:83-86)
   double Dobs;
-  if constexpr (OCC) Dobs = obs_distance_occ<NEED_GAP>(r, p, ov, oc, w.box);
+  int lk = 0;
+  if constexpr (OCC == 2) lk = roll_occ_layer(r, p, oc);
+  if constexpr (OCC != 0) Dobs = obs_distance_occ<NEED_GAP, OCC == 2>(r, p, ov, oc, w.box, lk);
   else Dobs = obs_distance<NEED_GAP>(r, p, ov, w.box);
   double Dcost = Dobs;
-  if constexpr (OCC && NEED_GAP)
-    Dcost = occ_cost_gap(oc, Dobs, r.x0 + 1.424 * r.c2, r.x1 + 1.424 * r.s2, r.x2, r.c2, r.s2);
+  if constexpr (OCC != 0 && NEED_GAP)
+    Dcost = occ_cost_gap<OCC == 2>(oc, lk, Dobs, r.x0 + 1.424 * r.c2, r.x1 + 1.424 * r.s2, r.x2, r.c2, r.s2);
   if (pc) pc->mark(4);
   return roll_step_post(r, p, Dobs, d2, Dcost);
 }
@@ -1217,7 +1227,7 @@ __device__ __forceinline__ void finish_rollout(const Roll& r, double c7, double 
 // One whole rollout from parent state `ps` along reference R (ref.v generated from pvb = Vstart).  rows
 // (nullable) receives stateArray: element k of row i at rows[(i * 10 + k) * es].  init (nullable)
 // receives the Simulation state after its constructor (reference end and velocity profile).
-template <bool NEED_GAP, bool OCC = false>
+template <bool NEED_GAP, int OCC = 0>
 __device__ __forceinline__ void run_rollout_ref(const St10& ps, const RefD& R, double pvb, int gb, const DevParams& p,
                                                 const ObsView& ov, OccView& oc, double* __restrict__ rows, int64_t es,
                                                 RollRes& out, WorkCtr& w, Roll* init = nullptr,
@@ -1338,13 +1348,13 @@ __device__ __forceinline__ ObsView stage_obstacles(const RollArgs& a, float4* ld
 #ifndef CLRRT_ROLLOUT_WAVES
 #define CLRRT_ROLLOUT_WAVES 1
 #endif
-template <int SRC, bool NEED_GAP, bool OCC = false>
+template <int SRC, bool NEED_GAP, int OCC = 0>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CLRRT_ROLLOUT_WAVES))) k_rollout(RollArgs a) {
   extern __shared__ float4 lds[];
   glibc::stage_tables();
   const ObsView ov = stage_obstacles<NEED_GAP>(a, lds);
   OccView oc{};
-  if constexpr (OCC) oc = occ_stage(a.occ, lds);
+  if constexpr (OCC != 0) oc = occ_stage<OCC == 2>(a.occ, lds);
   CLRRT_PARAMS_DECL(P);
   const int gt = blockIdx.x * blockDim.x + threadIdx.x;
   const int js = a.job_stride > 1 ? a.job_stride : 1;
@@ -1456,7 +1466,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CLRRT_
     __syncthreads();
     if (threadIdx.x < 3 && s_ctr[threadIdx.x]) atomicAdd(&a.ctr[threadIdx.x], s_ctr[threadIdx.x]);
   }
-  if constexpr (OCC) {  // work counter 3: steps that took the grid's exact scan
+  if constexpr (OCC != 0) {  // work counter 3: steps that took the grid's exact scan
     if (a.ctr && oc.scans) atomicAdd(&a.ctr[3], (unsigned long long)oc.scans);
   }
 #ifdef CLRRT_ROLL_PROFILE
@@ -1693,14 +1703,14 @@ constexpr int kFinSuspend = 1000;  // k_roll_run: `fin` of a lane whose chain re
 // it has none of that code (the step loop's register allocation is that of the plain kernel)
 // OCC: CLRRT_COLLISION_OCC with a grid set -- the step tests the occupancy grid (clrrt_occ.hpp) before the obstacle
 // list; the instantiations without it are the mode-1 kernels, none of that code in them
-template <bool NEED_GAP, bool COOP, bool CARRY, bool OCC = false>
+template <bool NEED_GAP, bool COOP, bool CARRY, int OCC = 0>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CLRRT_ROLL_WAVES))) k_roll_run(RollArgs a,
                                                   int* __restrict__ qnext, int* __restrict__ best, int B) {
   extern __shared__ float4 lds[];
   glibc::stage_tables();
   const ObsView ov = stage_obstacles<NEED_GAP>(a, lds);
   OccView oc{};
-  if constexpr (OCC) oc = occ_stage(a.occ, lds);
+  if constexpr (OCC != 0) oc = occ_stage<OCC == 2>(a.occ, lds);
   CLRRT_PARAMS_DECL(P);
   const int lane = threadIdx.x & 63;
   CoopLds cl{};
@@ -2001,13 +2011,15 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CLRRT_
       d2 = roll_step_pre(r, P, c7, c8, c9, w, pc);
     }
     double Dobs;
-    if constexpr (OCC && COOP) {  // a lane whose step hits the grid sits the cooperative box tests out
-      const bool hit = act && occ_hit(oc, r.x0 + 1.424 * r.c2, r.x1 + 1.424 * r.s2, r.x2, r.c2, r.s2);
+    int lk = 0;  // the step's layer, for the hit test and the clearance
+    if constexpr (OCC == 2) lk = roll_occ_layer(r, P, oc);
+    if constexpr (OCC != 0 && COOP) {  // a lane whose step hits the grid sits the cooperative box tests out
+      const bool hit = act && occ_hit<OCC == 2>(oc, lk, r.x0 + 1.424 * r.c2, r.x1 + 1.424 * r.s2, r.x2, r.c2, r.s2);
       Dobs = obs_distance_coop(act && !hit, r, P, ov, w.box, cl, a.ctr ? a.ctr + 33 : nullptr);
       if (!act) continue;
       if (hit) Dobs = 0.0;
-    } else if constexpr (OCC) {
-      Dobs = obs_distance_occ<NEED_GAP>(r, P, ov, oc, w.box);
+    } else if constexpr (OCC != 0) {
+      Dobs = obs_distance_occ<NEED_GAP, OCC == 2>(r, P, ov, oc, w.box, lk);
     } else if constexpr (COOP) {
       Dobs = obs_distance_coop(act, r, P, ov, w.box, cl, a.ctr ? a.ctr + 33 : nullptr);
       if (!act) continue;
@@ -2015,8 +2027,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CLRRT_
       Dobs = obs_distance<NEED_GAP>(r, P, ov, w.box);
     }
     double Dcost = Dobs;
-    if constexpr (OCC && NEED_GAP)
-      Dcost = occ_cost_gap(oc, Dobs, r.x0 + 1.424 * r.c2, r.x1 + 1.424 * r.s2, r.x2, r.c2, r.s2);
+    if constexpr (OCC != 0 && NEED_GAP)
+      Dcost = occ_cost_gap<OCC == 2>(oc, lk, Dobs, r.x0 + 1.424 * r.c2, r.x1 + 1.424 * r.s2, r.x2, r.c2, r.s2);
     if (pc) pc->mark(4);
     int o = roll_step_post(r, P, Dobs, d2, Dcost);
 #ifdef CLRRT_ROLL_PROFILE
@@ -2054,7 +2066,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CLRRT_
       atomicAdd(&a.ctr[1], v1);
       atomicAdd(&a.ctr[2], v2);
     }
-    if constexpr (OCC) {  // work counter 3: steps that took the grid's exact scan
+    if constexpr (OCC != 0) {  // work counter 3: steps that took the grid's exact scan
       unsigned long long v3 = oc.scans;
 #pragma unroll
       for (int q = 32; q > 0; q >>= 1) v3 += (unsigned long long)__shfl_xor((long long)v3, q, 64);
@@ -2663,12 +2675,15 @@ __device__ __forceinline__ double reinit_row(const DevParams& p, const ObsView& 
   glibc::sincos(r.x2, r.s2, r.c2);
   uint32_t tests = 0;
   double Dobs;
-  if constexpr (OCC) Dobs = obs_distance_occ<NEED_GAP>(r, p, ov, oc, tests);
+  int lk = 0;
+  if constexpr (OCC) lk = roll_occ_layer(r, p, oc);
+  if constexpr (OCC) Dobs = obs_distance_occ<NEED_GAP>(r, p, ov, oc, tests, lk);
   else Dobs = obs_distance<NEED_GAP>(r, p, ov, tests);
   if (Dobs == 0) on_hit();
   double Dcost = Dobs;
   if constexpr (OCC)
-    if (p.use_exp) Dcost = occ_cost_gap(oc, Dobs, r.x0 + 1.424 * r.c2, r.x1 + 1.424 * r.s2, r.x2, r.c2, r.s2);
+    if (p.use_exp)
+      Dcost = occ_cost_gap<true>(oc, lk, Dobs, r.x0 + 1.424 * r.c2, r.x1 + 1.424 * r.s2, r.x2, r.c2, r.s2);
   const double kappa = glibc::tan(x[3]) / p.L;
   double term = p.W0 * x[4] * p.dt + p.W1 * fabs(kappa);
   if (p.use_exp) term = term + p.W2 * glibc::exp(-p.W3 * Dcost);  // glibc's exp, restated
@@ -2684,7 +2699,7 @@ __device__ __forceinline__ double reinit_lane(const DevParams& p, const double* 
 template <bool OCC>
 __global__ void __launch_bounds__(256) k_tree_reinit(ReinitArgs a) {
   glibc::stage_tables();
-  OccView oc{&a.occ, a.occ.occ, a.occ.reach, 0u};  // (OCC: the maps are read from global memory)
+  OccView oc{&a.occ, a.occ.occ, a.occ.reach, 0u, nullptr};  // (OCC: the maps are read from global memory)
   __shared__ int s_kept, s_coll;
   __shared__ long long s_rows;
   const int tid = threadIdx.x;
@@ -2841,7 +2856,7 @@ __global__ void __launch_bounds__(256) k_rebase_check(RebaseCheck ra) {
   const RollArgs& a = ra.a;
   const ObsView ov = stage_obstacles<NEED_GAP>(a, lds);
   OccView oc{};
-  if constexpr (OCC) oc = occ_stage(a.occ, lds);
+  if constexpr (OCC) oc = occ_stage<true>(a.occ, lds);
   CLRRT_PARAMS_DECL(P);
   double sn, cs;
   glibc::sincos(ra.P2, sn, cs);
@@ -3265,23 +3280,24 @@ __global__ void k_obs_distance(DevParams p, const BakedObs* __restrict__ obs, co
   glibc::sincos(r.x2, r.s2, r.c2);
   uint32_t tests = 0;
   if constexpr (OCC) {
-    OccView oc{&og, og.occ, og.reach, 0u};
-    out[i] = obs_distance_occ<true>(r, p, ov, oc, tests);
+    OccView oc{&og, og.occ, og.reach, 0u, nullptr};
+    out[i] = obs_distance_occ<true>(r, p, ov, oc, tests, roll_occ_layer(r, p, oc));
   } else {
     out[i] = obs_distance<true>(r, p, ov, tests);
   }
 }
 
 // clrrt_occupancy_clearance: occ_clearance (the step loops' device function) for n states of 10 doubles, with the
-// heading's cosine and sine as the step holds them (glibc::sincos).
-__global__ void k_occ_clearance(OccGrid og, const double* __restrict__ st, int n, double* __restrict__ out) {
+// heading's cosine and sine as the step holds them (glibc::sincos), on the layer of the state's time (x[6] under
+// use_pred, else 0).
+__global__ void k_occ_clearance(OccGrid og, int use_pred, const double* __restrict__ st, int n, double* __restrict__ out) {
   glibc::stage_tables();
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const double* x = st + 10 * (int64_t)i;
   double sn, cs;
   glibc::sincos(x[2], sn, cs);
-  out[i] = occ_clearance(og, x[0] + 1.424 * cs, x[1] + 1.424 * sn, x[2], cs, sn);
+  out[i] = occ_clearance<true>(og, occ_layer(og, use_pred ? x[6] : 0.0), x[0] + 1.424 * cs, x[1] + 1.424 * sn, x[2], cs, sn);
 }
 
 // Test hook (clrrt_selftest_collision): the rollout kernels' collision decision for explicit states, one state
@@ -3300,7 +3316,7 @@ __global__ void __launch_bounds__(256) k_selftest_collision(RollArgs a, int path
   if (path != CLRRT_COLL_EXHAUSTIVE) ov = stage_obstacles<false>(a, lds);
   if (path == CLRRT_COLL_LANE_NOGRID) ov.gw = ov.gh = 0;
   OccView oc{};
-  if constexpr (OCC) oc = occ_stage(a.occ, lds);  // where a k_roll_run launch of these arguments holds the maps
+  if constexpr (OCC) oc = occ_stage<true>(a.occ, lds);  // where a k_roll_run launch of these arguments holds the maps
   CLRRT_PARAMS_DECL(P);
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   const bool act = i < n && active[i] != 0;
@@ -3323,13 +3339,14 @@ __global__ void __launch_bounds__(256) k_selftest_collision(RollArgs a, int path
     cl.q = (uint32_t*)(base + 64 * sizeof(Box4) + 64 * sizeof(double) + 64 * sizeof(int));
     cl.cap = COOP_QCAP;
     bool hit = false;
-    if constexpr (OCC) hit = act && occ_hit(oc, r.x0 + 1.424 * r.c2, r.x1 + 1.424 * r.s2, r.x2, r.c2, r.s2);
+    if constexpr (OCC)
+      hit = act && occ_hit<true>(oc, roll_occ_layer(r, P, oc), r.x0 + 1.424 * r.c2, r.x1 + 1.424 * r.s2, r.x2, r.c2, r.s2);
     const double Dc = obs_distance_coop(act && !hit, r, P, ov, cnt, cl);
     if (act) D = hit ? 0.0 : Dc;
   } else if (act) {
     if constexpr (OCC)
-      D = path == CLRRT_COLL_EXHAUSTIVE ? obs_distance_occ<true>(r, P, ov, oc, cnt)
-                                        : obs_distance_occ<false>(r, P, ov, oc, cnt);
+      D = path == CLRRT_COLL_EXHAUSTIVE ? obs_distance_occ<true>(r, P, ov, oc, cnt, roll_occ_layer(r, P, oc))
+                                        : obs_distance_occ<false>(r, P, ov, oc, cnt, roll_occ_layer(r, P, oc));
     else
       D = path == CLRRT_COLL_EXHAUSTIVE ? obs_distance<true>(r, P, ov, cnt) : obs_distance<false>(r, P, ov, cnt);
   }
@@ -3535,45 +3552,58 @@ bool roll_coop_applies(const RollArgs& a) {
          roll_obs_lds(a) + 4 * kCoopLdsPerWave <= 148 * 1024;
 }
 static size_t occ_place(OccGrid& g, size_t base, bool coop);
-bool roll_occ_in_lds(const RollArgs& a) {
+int roll_occ_placement(const RollArgs& a) {
   OccGrid g = a.occ;
   const bool coop = roll_coop_applies(a);
   occ_place(g, roll_obs_lds(a) + (coop ? 4 * kCoopLdsPerWave : 0), coop);
-  return g.in_lds != 0;
+  return g.in_lds;
 }
 
 // The occupancy maps' place in a rollout launch's dynamic LDS: behind `base` bytes of obstacle tables and
 // cooperative scratch when the whole stays within the 148 KB the kernels use beside the glibc tables' static LDS;
 // else the kernels read them from global memory.  The cooperative scratch counts whether the launch uses it or not
 // (`coop`: it does), so a grid's placement does not flip with the shape of the obstacle list.  Returns the launch's
-// dynamic LDS bytes.
-size_t occ_map_bytes(const OccGrid& g) { return sizeof(uint32_t) * ((size_t)g.h * g.ws + (size_t)g.rh * g.rws); }
+// dynamic LDS bytes.  A stack goes there whole -- all layers' two bitmaps -- under the same rule; one that does not fit
+// sends its union reach map alone when that fits (the step's first test then stays in LDS), else nothing.
+size_t occ_map_bytes(const OccGrid& g) {
+  return sizeof(uint32_t) * (size_t)g.layers * ((size_t)g.occ_stride + (size_t)g.reach_stride);
+}
+size_t occ_union_bytes(const OccGrid& g) { return sizeof(uint32_t) * (size_t)g.reach_stride; }
 static size_t occ_place(OccGrid& g, size_t base, bool coop) {
-  g.in_lds = 0;
+  g.in_lds = OCC_IN_GLOBAL;
   g.lds_off = 0;
   if (g.w <= 0) return base;
   const size_t off = (base + 15) / 16 * 16;
-  if (off + (coop ? 0 : 4 * kCoopLdsPerWave) + occ_map_bytes(g) > 148 * 1024) return base;
-  g.in_lds = 1;
-  g.lds_off = (int)off;
-  return off + occ_map_bytes(g);
+  const size_t room = off + (coop ? 0 : 4 * kCoopLdsPerWave);
+  if (room + occ_map_bytes(g) <= 148 * 1024) {
+    g.in_lds = OCC_IN_LDS;
+    g.lds_off = (int)off;
+    return off + occ_map_bytes(g);
+  }
+  if (g.layers > 1 && room + occ_union_bytes(g) <= 148 * 1024) {
+    g.in_lds = OCC_IN_LDS_UNION;
+    g.lds_off = (int)off;
+    return off + occ_union_bytes(g);
+  }
+  return base;
 }
 
-template <int SRC>
+// OCC: 1 a single grid, 2 a stack of more than one layer (the LAYERED twin: see obs_distance_occ).
+template <int SRC, int OCC>
 static hipError_t launch_roll_occ(hipStream_t st, const RollArgs& a0) {
   RollArgs a = a0;
   const size_t lds = occ_place(a.occ, a.p.need_gap ? 0 : roll_lds_bytes(a), false);
   const int64_t threads = (int64_t)a.njobs * (a.job_stride > 1 ? a.job_stride : 1);
   dim3 grid((unsigned)((threads + 255) / 256)), block(256);
-  const void* fn = a.p.need_gap ? (const void*)&k_rollout<SRC, true, true> : (const void*)&k_rollout<SRC, false, true>;
+  const void* fn = a.p.need_gap ? (const void*)&k_rollout<SRC, true, OCC> : (const void*)&k_rollout<SRC, false, OCC>;
   if (lds > 64 * 1024) {
     hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
   }
   if (a.p.need_gap)
-    hipLaunchKernelGGL((k_rollout<SRC, true, true>), grid, block, lds, st, a);
+    hipLaunchKernelGGL((k_rollout<SRC, true, OCC>), grid, block, lds, st, a);
   else
-    hipLaunchKernelGGL((k_rollout<SRC, false, true>), grid, block, lds, st, a);
+    hipLaunchKernelGGL((k_rollout<SRC, false, OCC>), grid, block, lds, st, a);
   LAUNCH_CHECK();
   return hipSuccess;
 }
@@ -3581,7 +3611,7 @@ static hipError_t launch_roll_occ(hipStream_t st, const RollArgs& a0) {
 template <int SRC>
 static hipError_t launch_roll_t(hipStream_t st, const RollArgs& a) {
   if (a.njobs <= 0) return hipSuccess;
-  if (a.occ.w > 0) return launch_roll_occ<SRC>(st, a);
+  if (a.occ.w > 0) return a.occ.layers > 1 ? launch_roll_occ<SRC, 2>(st, a) : launch_roll_occ<SRC, 1>(st, a);
   const size_t lds = roll_lds_bytes(a);
   const int64_t threads = (int64_t)a.njobs * (a.job_stride > 1 ? a.job_stride : 1);
   dim3 grid((unsigned)((threads + 255) / 256)), block(256);
@@ -3649,9 +3679,12 @@ hipError_t launch_rollout_persistent(hipStream_t st, const RollArgs& a0, int B, 
   const bool occ = a.occ.w > 0;  // CLRRT_COLLISION_OCC with a grid: the OCC instantiations
   const size_t lds = occ_place(a.occ, obs_lds + (coop ? 4 * kCoopLdsPerWave : 0), coop);
   const bool carry = a.cap > 0 || a.ncarry > 0;  // deferred samples: the CARRY instantiation
-  const void* fn = occ ? (a.p.need_gap ? (carry ? (const void*)&k_roll_run<true, false, true, true> : (const void*)&k_roll_run<true, false, false, true>)
-                          : coop       ? (carry ? (const void*)&k_roll_run<false, true, true, true> : (const void*)&k_roll_run<false, true, false, true>)
-                                       : (carry ? (const void*)&k_roll_run<false, false, true, true> : (const void*)&k_roll_run<false, false, false, true>))
+  const bool lay = a.occ.layers > 1;  // the LAYERED twin of the OCC instantiations (OCC 2)
+#define ROLL_RUN_OCC(G, C, Y) (lay ? (const void*)&k_roll_run<G, C, Y, 2> : (const void*)&k_roll_run<G, C, Y, 1>)
+  const void* fn = occ ? (a.p.need_gap ? (carry ? ROLL_RUN_OCC(true, false, true) : ROLL_RUN_OCC(true, false, false))
+                          : coop       ? (carry ? ROLL_RUN_OCC(false, true, true) : ROLL_RUN_OCC(false, true, false))
+                                       : (carry ? ROLL_RUN_OCC(false, false, true) : ROLL_RUN_OCC(false, false, false)))
+#undef ROLL_RUN_OCC
                    : a.p.need_gap ? (carry ? (const void*)&k_roll_run<true, false, true> : (const void*)&k_roll_run<true, false, false>)
                    : coop       ? (carry ? (const void*)&k_roll_run<false, true, true> : (const void*)&k_roll_run<false, true, false>)
                                 : (carry ? (const void*)&k_roll_run<false, false, true> : (const void*)&k_roll_run<false, false, false>);
@@ -3677,21 +3710,24 @@ hipError_t launch_rollout_persistent(hipStream_t st, const RollArgs& a0, int B, 
   } else {
     a.perm = nullptr;
   }
+#define ROLL_RUN_OCC(G, C, Y)                                                                                      \
+  do {                                                                                                             \
+    if (lay) hipLaunchKernelGGL((k_roll_run<G, C, Y, 2>), dim3(nb), dim3(256), lds, st, a, qnext, best, B);        \
+    else hipLaunchKernelGGL((k_roll_run<G, C, Y, 1>), dim3(nb), dim3(256), lds, st, a, qnext, best, B);            \
+  } while (0)
   if (occ) {
     if (carry) {
-      if (a.p.need_gap)
-        hipLaunchKernelGGL((k_roll_run<true, false, true, true>), dim3(nb), dim3(256), lds, st, a, qnext, best, B);
-      else if (coop)
-        hipLaunchKernelGGL((k_roll_run<false, true, true, true>), dim3(nb), dim3(256), lds, st, a, qnext, best, B);
-      else
-        hipLaunchKernelGGL((k_roll_run<false, false, true, true>), dim3(nb), dim3(256), lds, st, a, qnext, best, B);
+      if (a.p.need_gap) ROLL_RUN_OCC(true, false, true);
+      else if (coop) ROLL_RUN_OCC(false, true, true);
+      else ROLL_RUN_OCC(false, false, true);
     } else if (a.p.need_gap) {
-      hipLaunchKernelGGL((k_roll_run<true, false, false, true>), dim3(nb), dim3(256), lds, st, a, qnext, best, B);
+      ROLL_RUN_OCC(true, false, false);
     } else if (coop) {
-      hipLaunchKernelGGL((k_roll_run<false, true, false, true>), dim3(nb), dim3(256), lds, st, a, qnext, best, B);
+      ROLL_RUN_OCC(false, true, false);
     } else {
-      hipLaunchKernelGGL((k_roll_run<false, false, false, true>), dim3(nb), dim3(256), lds, st, a, qnext, best, B);
+      ROLL_RUN_OCC(false, false, false);
     }
+#undef ROLL_RUN_OCC
   } else if (carry) {
     if (a.p.need_gap)
       hipLaunchKernelGGL((k_roll_run<true, false, true>), dim3(nb), dim3(256), lds, st, a, qnext, best, B);
@@ -4015,31 +4051,38 @@ hipError_t launch_rebase_commit(hipStream_t st, const clrrt_node* hdr, int nk, c
 }
 
 hipError_t launch_occ_bake(hipStream_t st, const uint8_t* cells, const OccGrid& g, double Rc, unsigned int* count) {
-  const int64_t np = (int64_t)g.h * g.ws * 32, nr = (int64_t)g.rh * g.rws * 32;  // whole waves per row (ws, rws even)
-  hipLaunchKernelGGL(k_occ_pack, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st, cells, g.w, g.h, g.ws,
-                     const_cast<uint32_t*>(g.occ), count);
+  const int64_t np = (int64_t)g.h * g.ws * 32, nr = (int64_t)g.rh * g.rws * 32;
+  const unsigned L = (unsigned)g.layers;
+  hipLaunchKernelGGL(k_occ_pack, dim3((unsigned)((np + 255) / 256), L), dim3(256), 0, st, cells, g.w, g.h, g.ws,
+                     g.occ_stride, const_cast<uint32_t*>(g.occ), count);
   LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_occ_reach, dim3((unsigned)((nr + 255) / 256)), dim3(256), 0, st, g.occ, g.w, g.h, g.ws, g.rk,
-                     g.rm, Rc, g.rw, g.rh, g.rws, const_cast<uint32_t*>(g.reach));
+  hipLaunchKernelGGL(k_occ_reach, dim3((unsigned)((nr + 255) / 256), L), dim3(256), 0, st, g.occ, g.w, g.h, g.ws, g.rk,
+                     g.rm, Rc, g.rw, g.rh, g.rws, g.occ_stride, g.reach_stride, const_cast<uint32_t*>(g.reach));
   LAUNCH_CHECK();
+  if (g.reach_u != g.reach) {
+    hipLaunchKernelGGL(k_occ_reach_union, dim3((unsigned)((g.reach_stride + 255) / 256)), dim3(256), 0, st, g.reach,
+                       g.reach_stride, g.reach_stride, g.layers, const_cast<uint32_t*>(g.reach_u));
+    LAUNCH_CHECK();
+  }
   return hipSuccess;
 }
 
 hipError_t launch_occ_field(hipStream_t st, const OccGrid& g, uint16_t* rowd, uint32_t* rowmask, uint32_t* field) {
   const int64_t np = (int64_t)g.h * g.ws * 32, nc = (int64_t)g.w * g.h;
-  hipError_t e = hipMemsetAsync(rowmask, 0, 64 * sizeof(uint32_t), st);
+  const unsigned L = (unsigned)g.layers;
+  hipError_t e = hipMemsetAsync(rowmask, 0, 64 * sizeof(uint32_t) * L, st);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_occ_field_rows, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st, g.occ, g.w, g.h, g.ws, rowd,
-                     rowmask);
+  hipLaunchKernelGGL(k_occ_field_rows, dim3((unsigned)((np + 255) / 256), L), dim3(256), 0, st, g.occ, g.w, g.h, g.ws,
+                     g.occ_stride, rowd, rowmask);
   LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_occ_field_cols, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, st, rowd, rowmask, g.w, g.h,
-                     field);
+  hipLaunchKernelGGL(k_occ_field_cols, dim3((unsigned)((nc + 255) / 256), L), dim3(256), 0, st, rowd, rowmask, g.w, g.h,
+                     g.w * g.h, field);
   LAUNCH_CHECK();
   return hipSuccess;
 }
 
-hipError_t launch_occ_clearance(hipStream_t st, const OccGrid& g, const double* states, int n, double* out) {
-  hipLaunchKernelGGL(k_occ_clearance, dim3((n + 255) / 256), dim3(256), 0, st, g, states, n, out);
+hipError_t launch_occ_clearance(hipStream_t st, const OccGrid& g, int use_pred, const double* states, int n, double* out) {
+  hipLaunchKernelGGL(k_occ_clearance, dim3((n + 255) / 256), dim3(256), 0, st, g, use_pred, states, n, out);
   LAUNCH_CHECK();
   return hipSuccess;
 }

@@ -5,6 +5,9 @@
 // and sine, c the centre of an occupied cell, d = c - vp, u = d.x cs + d.y sn, v = d.y cs - d.x sn, the grid hits when
 // some occupied cell has |u| <= 2.424 + inflate and |v| <= 1 + inflate, all in double.  A non-finite vp or heading does
 // not hit.
+//
+// A stack of layers (clrrt_set_occupancy_layers) is `layers` such grids of one geometry, one per time slice: the bake
+// kernels take the layer from blockIdx.y, and a step tests the maps of the layer occ_layer gives for its time.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -18,9 +21,13 @@ namespace clrrt {
 
 // ------------------------------------------------------------------------------------------------ bake
 // Bytes -> bits: one lane per cell of a row padded to 64 cells (ws is even), so a wave's ballot is two whole words of
-// one row, stored by its first lane; the padding bits are 0.  The occupied cells are counted into *count.
-__global__ void __launch_bounds__(256) k_occ_pack(const uint8_t* __restrict__ cells, int w, int h, int ws,
+// one row, stored by its first lane; the padding bits are 0.  The occupied cells of layer blockIdx.y are counted into
+// count[blockIdx.y]; ostride: words per layer of occ.
+__global__ void __launch_bounds__(256) k_occ_pack(const uint8_t* __restrict__ cells, int w, int h, int ws, int ostride,
                                                   uint32_t* __restrict__ occ, unsigned int* __restrict__ count) {
+  cells += (int64_t)blockIdx.y * w * h;
+  occ += (int64_t)blockIdx.y * ostride;
+  count += blockIdx.y;
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int rowbits = ws * 32;
   const int64_t j = idx / rowbits;
@@ -49,8 +56,12 @@ __global__ void __launch_bounds__(256) k_occ_pack(const uint8_t* __restrict__ ce
 // centres within Rc of the square: every row whose centre line is within Rc of [ay, ay + rk] (one row of slack either
 // side), and on a row at distance dy the columns within sqrt(Rc^2 - dy^2) of [ax, ax + rk] (one column of slack).
 // A vp outside the map is more than rm rk >= Rc + rk cells from every centre: free.
+// Layer blockIdx.y: ostride / rstride words per layer of occ / reach.
 __global__ void __launch_bounds__(256) k_occ_reach(const uint32_t* __restrict__ occ, int w, int h, int ws, int rk, int rm,
-                                                   double Rc, int rw, int rh, int rws, uint32_t* __restrict__ reach) {
+                                                   double Rc, int rw, int rh, int rws, int ostride, int rstride,
+                                                   uint32_t* __restrict__ reach) {
+  occ += (int64_t)blockIdx.y * ostride;
+  reach += (int64_t)blockIdx.y * rstride;
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int rowbits = rws * 32;
   const int64_t rj = idx / rowbits;
@@ -85,6 +96,22 @@ __global__ void __launch_bounds__(256) k_occ_reach(const uint32_t* __restrict__ 
   }
 }
 
+// The union reach map of a stack: word q of uni is the bitwise OR of word q of every layer's reach map (n words per
+// layer, rstride apart).
+//
+// Why its clear bits are safe for every layer (a superset of a superset): layer k's reach map has a set bit wherever a
+// state can hit layer k (k_occ_reach's argument), so a bit that is clear in the OR is clear in every layer's map and
+// no state in that reach cell hits any layer -- whichever layer the step's time selects.  The step may therefore take
+// a clear union bit as free without knowing its layer; a set bit decides nothing and the layer's own maps follow.
+__global__ void __launch_bounds__(256) k_occ_reach_union(const uint32_t* __restrict__ reach, int n, int rstride,
+                                                         int layers, uint32_t* __restrict__ uni) {
+  const int q = blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= n) return;
+  uint32_t m = 0u;
+  for (int k = 0; k < layers; k++) m |= reach[(int64_t)k * rstride + q];
+  uni[q] = m;
+}
+
 // ------------------------------------------------------------------------------------------------ distance field
 // The squared Euclidean distance field of clrrt_set_occupancy_clearance: field[j w + i] = min over occupied cells
 // (i', j') of (i - i')^2 + (j - j')^2, exact in uint32 (at most 2 * 2047^2), OCC_FIELD_NONE without an occupied cell.
@@ -97,9 +124,13 @@ __global__ void __launch_bounds__(256) k_occ_reach(const uint32_t* __restrict__ 
 // every wave holds word q of the wave's row and the ballot of the non-zero ones; a cell's nearest occupied cell on
 // either side is in its own word (clz / ctz of the masked word) or in the nearest non-zero word on that side (clz /
 // ctz of the ballot, the word fetched by a shuffle).  The padding bits are 0.  Rows with an occupied cell are marked
-// in rowmask (bit j & 31 of word j >> 5).
-__global__ void __launch_bounds__(256) k_occ_field_rows(const uint32_t* __restrict__ occ, int w, int h, int ws,
+// in rowmask (bit j & 31 of word j >> 5).  Layer blockIdx.y: ostride words of occ, w h entries of rowd and 64 words
+// of rowmask per layer.
+__global__ void __launch_bounds__(256) k_occ_field_rows(const uint32_t* __restrict__ occ, int w, int h, int ws, int ostride,
                                                         uint16_t* __restrict__ rowd, uint32_t* __restrict__ rowmask) {
+  occ += (int64_t)blockIdx.y * ostride;
+  rowd += (int64_t)blockIdx.y * w * h;
+  rowmask += blockIdx.y * 64;
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int rowbits = ws * 32;
   const int64_t j = idx / rowbits;
@@ -150,10 +181,14 @@ __device__ __forceinline__ int occ_row_next(const uint32_t* __restrict__ m, int 
 // Column pass, one lane per cell, adjacent lanes on adjacent columns (the loads of a row coalesce): a windowed
 // minimum over the non-empty rows, outward from the cell's own row in both directions, that stops where (j - j')^2
 // alone reaches the best so far -- no row farther out can lower it.  The row skip makes a nearly empty map (the
-// window's worst case) cost a few rows per cell.
+// window's worst case) cost a few rows per cell.  Layer blockIdx.y: w h entries of rowd, 64 words of rowmask and
+// fstride dwords of field per layer.
 __global__ void __launch_bounds__(256) k_occ_field_cols(const uint16_t* __restrict__ rowd,
-                                                        const uint32_t* __restrict__ rowmask, int w, int h,
+                                                        const uint32_t* __restrict__ rowmask, int w, int h, int fstride,
                                                         uint32_t* __restrict__ field) {
+  rowd += (int64_t)blockIdx.y * w * h;
+  rowmask += blockIdx.y * 64;
+  field += (int64_t)blockIdx.y * fstride;
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= (int64_t)w * h) return;
   const int j = (int)(idx / w), i = (int)(idx % w);
@@ -182,41 +217,71 @@ __global__ void __launch_bounds__(256) k_occ_field_cols(const uint16_t* __restri
 
 // ------------------------------------------------------------------------------------------------ step test
 // The maps a kernel reads: the grid record (a kernel argument: scalar loads) and the two bitmaps, in LDS
-// (occ_stage) or global memory; scans counts the lane's steps that took the exact scan.
+// (occ_stage) or global memory; scans counts the lane's steps that took the exact scan.  uni: the union reach map in
+// LDS where the launch staged it alone (OCC_IN_LDS_UNION), else null.
 struct OccView {
   const OccGrid* g;
   const uint32_t* occ;
   const uint32_t* reach;
   uint32_t scans;
+  const uint32_t* uni;
 };
 
-// Copies both maps into the block's dynamic LDS at g.lds_off when the launch placed them there (every thread of
-// the block calls it; the caller's next barrier, or this one, orders the copy before the first step).
+// The layer of a step at time t (include/clrrt.h, clrrt_set_occupancy_layers): q = (t - t0) / dt in double (a
+// division); layer 0 when !(q >= 0) (times before t0, NaN, -inf), the last layer when q >= layers - 1 (+inf too),
+// (int)q between.  One layer: 0 by the same rule, without the arithmetic.
+__device__ __forceinline__ int occ_layer(const OccGrid& g, double t) {
+  if (g.layers <= 1) return 0;
+  const double q = (t - g.t0) / g.dt;
+  if (!(q >= 0.0)) return 0;
+  if (q >= (double)(g.layers - 1)) return g.layers - 1;
+  return (int)q;
+}
+
+// Copies the maps into the block's dynamic LDS at g.lds_off when the launch placed them there -- every layer's two
+// bitmaps (OCC_IN_LDS), or the union reach map alone (OCC_IN_LDS_UNION) -- (every thread of the block calls it; the
+// caller's next barrier, or this one, orders the copy before the first step).
+// LAYERED: the instantiation serves a stack of more than one layer (the launch picks it by g.layers); without it the
+// code is the single grid's -- no layer arithmetic, no strides, no union map.
+template <bool LAYERED>
 __device__ __forceinline__ OccView occ_stage(const OccGrid& g, void* lds_base) {
-  OccView v{&g, g.occ, g.reach, 0u};
-  if (g.in_lds) {
+  OccView v{&g, g.occ, g.reach, 0u, nullptr};
+  if (g.in_lds == OCC_IN_LDS) {
     uint32_t* o = (uint32_t*)((char*)lds_base + g.lds_off);
-    const int no = g.h * g.ws, nr = g.rh * g.rws;
+    const int no = LAYERED ? g.layers * g.occ_stride : g.h * g.ws, nr = LAYERED ? g.layers * g.reach_stride : g.rh * g.rws;
     for (int q = threadIdx.x; q < no; q += blockDim.x) o[q] = g.occ[q];
     for (int q = threadIdx.x; q < nr; q += blockDim.x) o[no + q] = g.reach[q];
     __syncthreads();
     v.occ = o;
     v.reach = o + no;
+  } else if (LAYERED && g.in_lds == OCC_IN_LDS_UNION) {
+    uint32_t* o = (uint32_t*)((char*)lds_base + g.lds_off);
+    const int nr = g.reach_stride;
+    for (int q = threadIdx.x; q < nr; q += blockDim.x) o[q] = g.reach_u[q];
+    __syncthreads();
+    v.uni = o;
   }
   return v;
 }
 
-// One step's grid decision for the vehicle box centre (vpx, vpy) and heading th with cosine cs and sine sn: the
-// reach-map bit at vp (clear: free, the open-space path), else the occupied cells inside the axis-aligned bounds
-// of the inflated box (one cell of slack: the exact test below decides), taken word by word and bit by bit.
-__device__ __forceinline__ bool occ_hit(OccView& ov, double vpx, double vpy, double th, double cs, double sn) {
+// One step's grid decision against layer k for the vehicle box centre (vpx, vpy) and heading th with cosine cs and
+// sine sn: the reach-map bit at vp (clear: free, the open-space path), else the occupied cells inside the axis-aligned
+// bounds of the inflated box (one cell of slack: the exact test below decides), taken word by word and bit by bit.
+// Where the launch staged the union reach map alone, its bit in LDS comes first (clear: free for every layer, no
+// global memory touched), then the layer's reach bit and occupancy words in global memory.
+template <bool LAYERED>
+__device__ __forceinline__ bool occ_hit(OccView& ov, int k, double vpx, double vpy, double th, double cs, double sn) {
   const OccGrid& g = *ov.g;
   if (!(isfinite(vpx) && isfinite(vpy) && isfinite(th))) return false;
   const double fx = (vpx - g.rx0) / g.rres, fy = (vpy - g.ry0) / g.rres;
   if (!(fx >= 0.0 && fx < (double)g.rw && fy >= 0.0 && fy < (double)g.rh)) return false;
   const int ix = (int)fx, iy = (int)fy;
-  if (!((ov.reach[iy * g.rws + (ix >> 5)] >> (ix & 31)) & 1u)) return false;
+  const int rq = iy * g.rws + (ix >> 5);
+  if constexpr (LAYERED)
+    if (ov.uni && !((ov.uni[rq] >> (ix & 31)) & 1u)) return false;
+  if (!((ov.reach[(LAYERED ? k * g.reach_stride : 0) + rq] >> (ix & 31)) & 1u)) return false;
   ov.scans++;
+  const uint32_t* const occ = LAYERED ? ov.occ + k * g.occ_stride : ov.occ;
   const double A = OCC_VEH_A + g.inflate, B = OCC_VEH_B + g.inflate;
   const double ex = fabs(cs) * A + fabs(sn) * B, ey = fabs(sn) * A + fabs(cs) * B;
   // (vp lies inside the reach map, so these quotients are small numbers: the casts are in range)
@@ -227,7 +292,7 @@ __device__ __forceinline__ bool occ_hit(OccView& ov, double vpx, double vpy, dou
   const int j0 = (int)fmax(jlo, 0.0), j1 = (int)fmin(jhi, (double)(g.h - 1));
   for (int j = j0; j <= j1; j++) {
     const double dy = (g.y0 + (j + 0.5) * g.res) - vpy;
-    const uint32_t* row = ov.occ + j * g.ws;
+    const uint32_t* row = occ + j * g.ws;
     for (int q = i0 >> 5; q <= (i1 >> 5); q++) {
       uint32_t m = row[q];
       if (q == (i0 >> 5)) m &= ~0u << (i0 & 31);
@@ -244,22 +309,24 @@ __device__ __forceinline__ bool occ_hit(OccView& ov, double vpx, double vpy, dou
   return false;
 }
 
-// One step's clearance from the distance field g.field (non-null; include/clrrt.h, clrrt_set_occupancy_clearance):
+// One step's clearance from layer k of the distance field g.field (non-null; include/clrrt.h, clrrt_set_occupancy_clearance):
 // three circles of radius OCC_CLR_RC along the heading cover the vehicle box; each centre inside the grid reads its
 // cell's squared distance (one dword from global memory), the smallest one gives the distance -- sqrt and the
 // product with res are monotonic, so the minimum is taken over the integers -- and a centre outside the grid, a
 // non-finite state or a map without an occupied cell leaves +inf, which the cap turns into clear_max.  All in double.
 #define OCC_CLR_RC 1.2857 /* circle radius: half width 1 and a third of the half length, 0.808, under one hypotenuse */
 #define OCC_CLR_S 1.616   /* spacing of the circle centres along the box axis */
-__device__ __forceinline__ double occ_clearance(const OccGrid& g, double vpx, double vpy, double th, double cs,
+template <bool LAYERED>
+__device__ __forceinline__ double occ_clearance(const OccGrid& g, int layer, double vpx, double vpy, double th, double cs,
                                                 double sn) {
   uint32_t m = OCC_FIELD_NONE;
+  const uint32_t* const field = LAYERED ? g.field + (int64_t)layer * g.field_stride : g.field;
   if (isfinite(vpx) && isfinite(vpy) && isfinite(th)) {
 #pragma unroll
     for (int k = -1; k <= 1; k++) {
       const double px = k ? vpx + (k * OCC_CLR_S) * cs : vpx, py = k ? vpy + (k * OCC_CLR_S) * sn : vpy;
       const double fx = (px - g.x0) / g.res, fy = (py - g.y0) / g.res;
-      if (fx >= 0.0 && fx < (double)g.w && fy >= 0.0 && fy < (double)g.h) m = min(m, g.field[(int)fy * g.w + (int)fx]);
+      if (fx >= 0.0 && fx < (double)g.w && fy >= 0.0 && fy < (double)g.h) m = min(m, field[(int)fy * g.w + (int)fx]);
     }
   }
   const double d = m == OCC_FIELD_NONE ? (double)INFINITY : g.res * sqrt((double)m);
@@ -271,10 +338,11 @@ __device__ __forceinline__ double occ_clearance(const OccGrid& g, double vpx, do
 // The value the obstacle cost term takes for a step that does not collide (Dobs != 0): min(Dobs, clearance) where
 // the field is baked and on, Dobs otherwise.  It does not pass through the collision test (the circles overhang the
 // box, so the clearance can be 0 on a state that does not hit).
-__device__ __forceinline__ double occ_cost_gap(const OccView& ov, double Dobs, double vpx, double vpy, double th,
-                                               double cs, double sn) {
+template <bool LAYERED>
+__device__ __forceinline__ double occ_cost_gap(const OccView& ov, int layer, double Dobs, double vpx, double vpy,
+                                               double th, double cs, double sn) {
   if (ov.g->field == nullptr || Dobs == 0) return Dobs;
-  const double c = occ_clearance(*ov.g, vpx, vpy, th, cs, sn);
+  const double c = occ_clearance<LAYERED>(*ov.g, layer, vpx, vpy, th, cs, sn);
   return c < Dobs ? c : Dobs;
 }
 

@@ -229,8 +229,8 @@ int clrrt_set_obstacles(clrrt_ctx* ctx, const clrrt_obstacle* obs, int32_t m);
  * v = d.y cos - d.x sin, the grid hits when some occupied cell has |u| <= 2.424 + inflate and |v| <= 1 + inflate
  * (double arithmetic throughout); a non-finite vp or heading does not hit.  On a hit checkObsDistance is 0 (the
  * rollout fails with fail_collision; no box test is made or counted); otherwise it is what CLRRT_COLLISION_OBB gives
- * for the same state and obstacle list.  The grid does not move with obs_use_pred; moving obstacles stay boxes.
- * Mode 2 without a grid is mode 1. */
+ * for the same state and obstacle list.  A single grid does not move with obs_use_pred; moving obstacles stay boxes,
+ * or become cells of a stack of time layers (clrrt_set_occupancy_layers below).  Mode 2 without a grid is mode 1. */
 typedef struct {
   double x0, y0;   /* car-frame position of the corner of cell (0, 0) */
   double res;      /* cell size [m], > 0 */
@@ -243,11 +243,41 @@ typedef struct {
  * lands the deferred rows of committed nodes (they were committed against the old scene).  Legal in any collision
  * mode; the grid is read only in mode 2.  Under sharding every rank sets the same grid. */
 int clrrt_set_occupancy(clrrt_ctx* ctx, const clrrt_occupancy* occ, const uint8_t* cells);
+/* A stack of time layers: predicted grids of the movers, one per time slice (engine extension; clrrt_set_occupancy is
+ * the stack with one layer and replaces whatever stack was set, and with one layer every launch and every result is
+ * what it is without this call).  cells holds `layers` grids of h rows of w bytes, layer k at cells + k w h; all
+ * layers share x0, y0, res, inflate, w, h.  1 <= layers <= CLRRT_OCC_MAX_LAYERS, w h layers <= 2^24 (and the limits
+ * of clrrt_set_occupancy on w, h, w h), t0 finite, dt finite and > 0; CLRRT_EINVAL names the field at fault (layers,
+ * w * h * layers, t0, dt, or one of clrrt_set_occupancy's), and the context is then unchanged.  occ == NULL or
+ * occ->w == 0 clears the stack.
+ *   Layer of a state x.  t = obs_use_pred ? x[6] : 0.0, the very value the same step gives the moving boxes;
+ * q = (t - t0) / dt in double (a division, not a product with a reciprocal); k = 0 when !(q >= 0) (NaN and -inf
+ * too), k = layers - 1 when q >= layers - 1 (+inf too), otherwise k = (int) q.  So layer 0 also serves the times
+ * before t0 and the last layer everything after the stack ends.
+ *   Decision.  The hit test above against layer k's cells; everything else of mode 2 is unchanged (a hit is
+ * checkObsDistance 0 with no box test made or counted, otherwise mode 1's value; a non-finite vp or heading does not
+ * hit).  Clearance (clrrt_set_occupancy_clearance): one distance field per layer (4 w h layers bytes in global
+ * memory), a state reads layer k's; everything else as written there.
+ *   Who picks the layer.  Every consumer of the grid, by the rule above: the rollouts of clrrt_expand,
+ * clrrt_rollout_batch and clrrt_simulate; clrrt_obstacle_distance, clrrt_selftest_collision and
+ * clrrt_occupancy_clearance; the re-init rows of clrrt_tree_init_from_path; the revalidation and re-costing rows of
+ * clrrt_tree_rebase, each by its own row[6] after the t_shift.
+ *   The stack is in the query's car frame and t0 on the rollouts' clock (x[6], 0 at the root).  Same preconditions as
+ * clrrt_set_occupancy: it first lands the deferred rows of committed nodes; legal in any collision mode, read only in
+ * mode 2; under sharding every rank sets the same stack. */
+#define CLRRT_OCC_MAX_LAYERS 16
+int clrrt_set_occupancy_layers(clrrt_ctx* ctx, const clrrt_occupancy* occ, int32_t layers, double t0, double dt,
+                               const uint8_t* cells);
 /* The grid as baked.  placement: where the persistent rollout kernel of the current parameters and obstacles
- * holds the two bitmaps. */
+ * holds the two bitmaps: all layers' in LDS (CLRRT_OCC_LDS, under the rule a single grid has always had); or, for a
+ * stack that does not fit, the bitwise OR of the layers' reach maps alone in LDS (CLRRT_OCC_REACH_LDS: a clear union
+ * bit is free for every layer and touches no global memory, else the layer's reach bit and then its occupancy words
+ * are read from global memory); or everything in global memory (CLRRT_OCC_GLOBAL).  On a stack, occupied and
+ * map_bytes are totals over the layers. */
 #define CLRRT_OCC_NONE 0
 #define CLRRT_OCC_LDS 1
 #define CLRRT_OCC_GLOBAL 2
+#define CLRRT_OCC_REACH_LDS 3
 typedef struct {
   int32_t w, h;            /* 0, 0: no grid */
   int32_t reach_w, reach_h; /* reach map cells */
@@ -258,6 +288,17 @@ typedef struct {
   double bake_ms;          /* device time of the last bake (upload + kernels) */
 } clrrt_occupancy_info_t;
 int clrrt_occupancy_info(clrrt_ctx* ctx, clrrt_occupancy_info_t* out);
+typedef struct {
+  int32_t layers;             /* 0: no grid */
+  int32_t placement;          /* CLRRT_OCC_* */
+  double t0, dt;              /* as set (a single grid: 0, 1) */
+  int64_t occupied[CLRRT_OCC_MAX_LAYERS]; /* occupied cells per layer */
+  int64_t map_bytes;          /* all layers' two bitmaps */
+  int64_t union_reach_bytes;  /* the union reach map (0 with one layer: it is the layer's reach map) */
+  int64_t field_bytes;        /* 4 w h layers when a field is baked, else 0 */
+  double bake_ms;             /* device time of the last bake (upload + kernels) */
+} clrrt_occupancy_layers_info_t;
+int clrrt_occupancy_layers_info(clrrt_ctx* ctx, clrrt_occupancy_layers_info_t* out);
 /* Occupancy clearance: the grid's distance in the obstacle cost term (engine extension; off by default, and with it
  * off every result and every launch is what it is without these functions).
  *   Field.  f[j][i] = min over occupied cells (i', j') of (i - i')^2 + (j - j')^2, an exact integer held as uint32;
@@ -285,14 +326,16 @@ typedef struct {
   double clear_max;     /* 0: off */
   int32_t on;           /* clear_max > 0 */
   int32_t baked;        /* a field of the current grid is on the device */
-  int64_t field_bytes;  /* 4 w h when baked, else 0 */
+  int64_t field_bytes;  /* 4 w h layers when baked, else 0 */
   double bake_ms;       /* device time of the last field bake (its kernels only) */
 } clrrt_clearance_info_t;
 int clrrt_occupancy_clearance_info(clrrt_ctx* ctx, clrrt_clearance_info_t* out);
-/* The w h field values, row j at out + j w.  CLRRT_ESTATE without a baked field. */
+/* The w h field values of layer 0 / of `layer`, row j at out + j w.  CLRRT_ESTATE without a baked field, CLRRT_EINVAL
+ * for a layer outside the stack. */
 int clrrt_occupancy_field(clrrt_ctx* ctx, uint32_t* out);
-/* c of n states (10 doubles each), evaluated on the device by the device function the step loops call.  CLRRT_ESTATE
- * without a baked field. */
+int clrrt_occupancy_field_layer(clrrt_ctx* ctx, int32_t layer, uint32_t* out);
+/* c of n states (10 doubles each), each on the layer its time selects, evaluated on the device by the device function
+ * the step loops call.  CLRRT_ESTATE without a baked field. */
 int clrrt_occupancy_clearance(clrrt_ctx* ctx, const double* states, int32_t n, double* out);
 int clrrt_set_rank(clrrt_ctx* ctx, int32_t rank);
 

@@ -177,11 +177,17 @@ class Engine {
   }
 
   /* The static occupancy grid of CLRRT_COLLISION_OCC (clrrt_set_occupancy; car frame): cells = h rows of w bytes,
-   * non-zero = occupied; occ.w == 0 or cells == nullptr clears it.  Read only when params().collision_mode is 2. */
-  void setOccupancy(const clrrt_occupancy& occ, const uint8_t* cells) {
+   * non-zero = occupied; occ.w == 0 or cells == nullptr clears it.  Read only when params().collision_mode is 2.
+   * layers > 1: a stack of time layers (clrrt_set_occupancy_layers), cells = layers grids one after the other, layer k
+   * serving the rollout times t0 + k dt <= t < t0 + (k + 1) dt. */
+  void setOccupancy(const clrrt_occupancy& occ, const uint8_t* cells, int32_t layers = 1, double t0 = 0.0,
+                    double dt = 0.0) {
     drop_cache();
     const bool clear = occ.w == 0 || !cells;
-    check(ctx_, clrrt_set_occupancy(ctx_, clear ? nullptr : &occ, clear ? nullptr : cells), "clrrt_set_occupancy");
+    if (layers > 1 && !clear)
+      check(ctx_, clrrt_set_occupancy_layers(ctx_, &occ, layers, t0, dt, cells), "clrrt_set_occupancy_layers");
+    else
+      check(ctx_, clrrt_set_occupancy(ctx_, clear ? nullptr : &occ, clear ? nullptr : cells), "clrrt_set_occupancy");
   }
   /* The occupancy clearance (clrrt_set_occupancy_clearance): clear_max > 0 puts the grid's distance into the obstacle
    * cost term of mode 2, capped at clear_max; 0 turns it off. */
@@ -735,7 +741,9 @@ struct TreeMarker {             /* createStateMsg(nodeid, tree[nodeid].tra, goal
 
 struct OccupancyGrid {          /* the static world as a lidar / camera occupancy grid, in the car frame of the query */
   clrrt_occupancy dims = {0, 0, 0, 0, 0, 0};  /* corner, cell size, inflate, w, h (include/clrrt.h); w == 0: none */
-  std::vector<uint8_t> cells;   /* h rows of w bytes, non-zero = occupied */
+  std::vector<uint8_t> cells;   /* layers grids of h rows of w bytes, non-zero = occupied */
+  int32_t layers = 1;           /* > 1: predicted grids of the movers, one per time slice (clrrt_set_occupancy_layers) */
+  double t0 = 0, dt = 0;        /* layer k serves t0 + k dt <= t < t0 + (k + 1) dt on the rollouts' clock (0 at the root) */
 };
 
 struct PlanReport {
@@ -810,11 +818,12 @@ class MotionPlanner {
     for (const auto& d : det) det_.push_back(obstacle_to_c(d));
   }
   /* The occupancy-grid form of updateObstacles (the note at motionplanner.cpp:80-82): the static world in the car
-   * frame of the next query, applied at the next planMotion beside the detections (which stay boxes); an empty grid
-   * (dims.w == 0) clears it.  Under sharding every rank is given the same grid. */
+   * frame of the next query, applied at the next planMotion beside the detections (which stay boxes, unless the
+   * grid is a stack of time layers that carries them as cells: grid.layers > 1); an empty grid (dims.w == 0) clears it.  Under sharding every rank is given the same grid. */
   void updateOccupancy(const OccupancyGrid& grid) {
-    if (grid.dims.w != 0 && grid.cells.size() < (size_t)grid.dims.w * (size_t)std::max(grid.dims.h, 0))
-      throw Error("updateOccupancy: fewer than w * h cells");
+    if (grid.dims.w != 0 && grid.cells.size() < (size_t)grid.dims.w * (size_t)std::max(grid.dims.h, 0) *
+                                                    (size_t)std::max(grid.layers, 1))
+      throw Error("updateOccupancy: fewer than w * h * layers cells");
     grid_ = grid;
     grid_dirty_ = true;
   }
@@ -845,8 +854,12 @@ class MotionPlanner {
     check(ctx_, clrrt_set_obstacles(ctx_, det_.data(), (int32_t)det_.size()), "clrrt_set_obstacles");  // RRT.det
     if (grid_dirty_) {
       const bool none = grid_.dims.w == 0;
-      check(ctx_, clrrt_set_occupancy(ctx_, none ? nullptr : &grid_.dims, none ? nullptr : grid_.cells.data()),
-            "clrrt_set_occupancy");
+      if (!none && grid_.layers > 1)
+        check(ctx_, clrrt_set_occupancy_layers(ctx_, &grid_.dims, grid_.layers, grid_.t0, grid_.dt, grid_.cells.data()),
+              "clrrt_set_occupancy_layers");
+      else
+        check(ctx_, clrrt_set_occupancy(ctx_, none ? nullptr : &grid_.dims, none ? nullptr : grid_.cells.data()),
+              "clrrt_set_occupancy");
       grid_dirty_ = false;
     }
     if (clear_dirty_) {

@@ -17,7 +17,13 @@ grid's exact scan (raw work counter 3 over work counter 0), nodes grown.  Then t
 With 2gc among the modes, the field bake time (clrrt_occupancy_clearance_info) of 512 x 512 and 2048 x 2048 grids at
 1 % random fill and with a single occupied cell follows.
 
-  python tools/occ_bench.py [--runs 3] [--modes 1,2,2g,2gc] [--out profiles/occ_grid.txt] [--label text]
+  mode 2L4 / 2L8  the static scene plus the 20 movers of urban_scene(200, 20), rasterised into 4 / 8 layers of 0.5 s
+           from t = 0 (scenes.rasterize_layers, clrrt_set_occupancy_layers), no obstacle list
+  mode 2m  that scene with the static boxes as the single grid and the 20 movers as boxes of the obstacle list: the
+           like-for-like cost of cells against boxes for 2L4
+With 2L8 among the modes, the bake time of stacks of 512 x 512 x 8 and 2048 x 512 x 16 (2 % fill) follows.
+
+  python tools/occ_bench.py [--runs 3] [--modes 1,2,2g,2gc,2L4,2L8,2m] [--out profiles/occ_grid.txt] [--label text]
 """
 import argparse
 import os
@@ -35,6 +41,10 @@ B, ROUNDS, DEFER = 16384, 8, 128
 GRID = dict(x0=0.0, y0=-26.0, res=0.2, w=330, h=260)
 
 
+LAYER_T0, LAYER_DT = 0.0, 0.5
+PLACES = {1: "LDS", 2: "global memory", 3: "global memory, the union reach map in LDS"}
+
+
 def grow(mode, obs, cells, w2=0.0, clear_max=0.0):
     params = clrrt.default_params(collision_mode=mode)
     params.Wcost[2] = w2
@@ -42,7 +52,9 @@ def grow(mode, obs, cells, w2=0.0, clear_max=0.0):
     try:
         pl.set_option("defer_steps", DEFER)
         pl.set_obstacles(obs)
-        if cells is not None:
+        if cells is not None and cells.ndim == 3:
+            pl.set_occupancy_layers(GRID["x0"], GRID["y0"], GRID["res"], cells, LAYER_T0, LAYER_DT)
+        elif cells is not None:
             pl.set_occupancy(GRID["x0"], GRID["y0"], GRID["res"], cells)
         if clear_max:
             pl.set_occupancy_clearance(clear_max)
@@ -67,6 +79,20 @@ def bake(n, runs):
         for _ in range(runs + 1):  # the first call allocates
             pl.set_occupancy(-0.05 * n, -0.05 * n, 0.1, cells)
             out.append(pl.occupancy_info())
+        return out[1:]
+    finally:
+        pl.close()
+
+
+def bake_stack(w, h, layers, runs):
+    cells = (np.random.default_rng(w + layers).random((layers, h, w)) < 0.02).astype(np.uint8)
+    pl = clrrt.Planner(clrrt.default_params(collision_mode=abi.CLRRT_COLLISION_OCC), max_nodes=1 << 10,
+                       max_rows=1 << 14, max_batch=64)
+    try:
+        out = []
+        for _ in range(runs + 1):  # the first call allocates
+            pl.set_occupancy_layers(-0.05 * w, -0.05 * h, 0.1, cells, LAYER_T0, LAYER_DT)
+            out.append(pl.occupancy_layers_info())
         return out[1:]
     finally:
         pl.close()
@@ -101,15 +127,24 @@ def main():
     obs = scenes.urban_scene(200)
     lines = [f"occ_bench {args.label}: cfg3 scene (200 static boxes), {B} samples x {ROUNDS} rounds, defer_steps {DEFER}; "
              f"library {os.path.relpath(clrrt.LIB_PATH, ROOT)}"]
+    layered = hasattr(clrrt.Planner, "set_occupancy_layers")
     for name in (m for m in args.modes.split(",") if m):
         mode = int(name[0])
         if mode == 2 and not hasattr(abi, "CLRRT_COLLISION_OCC"):
             continue
         if name == "2gc" and not hasattr(clrrt.Planner, "set_occupancy_clearance"):
             continue
+        if name.startswith("2L") and not layered:
+            continue
         cells = scenes.rasterize(obs, **GRID) if mode == 2 else None
-        res = [grow(mode, obs if mode == 1 else obs[:0], cells, 2.0 if "g" in name else 0.0,
-                    3.0 if name == "2gc" else 0.0) for _ in range(args.runs)]
+        boxes = obs if mode == 1 else obs[:0]
+        if name.startswith("2L"):
+            cells = scenes.rasterize_layers(scenes.urban_scene(200, 20), layers=int(name[2:]), t0=LAYER_T0, dt=LAYER_DT,
+                                            **GRID)
+        elif name == "2m":
+            boxes = scenes.urban_scene(200, 20)[200:]
+        res = [grow(mode, boxes, cells, 2.0 if "g" in name else 0.0, 3.0 if name == "2gc" else 0.0)
+               for _ in range(args.runs)]
         ms = [r["ms_per_launch"] for r in res]
         lines.append(f"mode {name}: rollout kernel ms per launch {' '.join('%.3f' % v for v in ms)} (spread "
                      f"{(max(ms) - min(ms)) / min(ms) * 100:.1f} %), launches {res[0]['launches']}, nodes "
@@ -118,8 +153,19 @@ def main():
             r = res[0]
             lines.append(f"mode 2: grid {GRID['w']} x {GRID['h']} at res {GRID['res']}, {r['info']['occupied']} occupied "
                          f"cells, maps {r['info']['map_bytes']} B in "
-                         f"{'LDS' if r['info']['placement'] == abi.OCC_LDS else 'global memory'}; exact scans "
+                         f"{PLACES[r['info']['placement']]}; exact scans "
                          f"{r['scans']} of {r['steps']} steps ({100.0 * r['scans'] / max(1, r['steps']):.2f} %)")
+        if name.startswith("2L") or name == "2m":
+            r = res[0]
+            lines.append(f"mode {name}: {r['info']['occupied']} occupied cells in all layers, maps "
+                         f"{r['info']['map_bytes']} B in {PLACES[r['info']['placement']]}; exact scans {r['scans']} of "
+                         f"{r['steps']} steps ({100.0 * r['scans'] / max(1, r['steps']):.2f} %)")
+    if "2L8" in args.modes.split(",") and layered:
+        for w, h, layers in ((512, 512, 8), (2048, 512, 16)):
+            b = bake_stack(w, h, layers, args.runs)
+            lines.append(f"stack bake {w} x {h} x {layers} (2 % fill, maps {b[0]['map_bytes']} B, union reach map "
+                         f"{b[0]['union_reach_bytes']} B, {PLACES[b[0]['placement']]}): "
+                         f"{' '.join('%.3f' % v['bake_ms'] for v in b)} ms (upload + kernels)")
     if "2" in args.modes.split(","):
         for n in (512, 2048):
             b = bake(n, args.runs)
